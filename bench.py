@@ -4,8 +4,14 @@
 (BASELINE.json metric, config[1] "1xMI355X dense grid: 1000 synthetic 640x480 frames into
 512^3 @2cm"; config[2] for the hash numbers).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what `value` needs and no more: it generates the frames, heats the clock, runs the
+W warm-up and K timed steps of the dense grid, writes the volume they left if --dump-outputs asks
+(a fixed seeded sample of its voxels, DIR/<name>.npy) and prints the line.  Everything else below
+(the cold window, the hash leg, ingest, drop-in, mesh, lounge and CPU-baseline legs) runs with
+--full, and is null in a plain run's line.
 
 A step is one launch's batch of frames (the unit the kernels fuse: one three-stage k_fused launch
 integrates 32 frames with the brick state held in registers; TSDFVolume.frames_per_launch).  The F synthetic frames
@@ -102,8 +108,36 @@ def parse():
     ap.add_argument("--preheat-ms", type=float, default=300.0,
                     help="clock warm-up: untimed integrate launches on the volume (then reset) before the "
                          "W warm-up steps; 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the cold window, the hash leg, "
+                         "host-frame ingest, drop-in calls, mesh extraction, the lounge frames and the CPU "
+                         "baseline (each with its own --no-... switch); without it only the dense steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the volume they left (tsdf, weight, colour at a fixed "
+                         "seeded sample of voxels, float32) to DIR/<name>.npy")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)  # tests: ranks, no GPU
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_hash = args.no_cpu = args.no_ingest = args.no_dropin = args.no_mesh = args.no_lounge = True
+    return args
+
+
+DUMP_SAMPLE = 1 << 21  # voxels --dump-outputs keeps of each array (40 MB in all)
+DUMP_SEED = 20251
+
+
+def dump_outputs(vol, out_dir, rank, n):
+    """--dump-outputs: what a caller of the timed path receives after its last step, the volume's
+    (tsdf, weight, colour) of TSDFVolume.get_state(), at a fixed seeded sample of this rank's voxels
+    (the whole 512^3 state is 1.6 GB): DIR/<name>.npy float32, and the sampled flat C-order voxel
+    indices as float64 (exact below 2^53).  Ranks of a sharded run write <name>.rank<r>.npy."""
+    t, w, c = vol.get_state()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.size, size=min(DUMP_SAMPLE, t.size)))
+    os.makedirs(out_dir, exist_ok=True)
+    tail = f".rank{rank}" if n > 1 else ""
+    for name, a in (("tsdf", t), ("weight", w), ("color", c)):
+        np.save(os.path.join(out_dir, f"{name}{tail}.npy"), np.ascontiguousarray(a.reshape(-1)[idx], dtype=np.float32))
+    np.save(os.path.join(out_dir, f"voxel_index{tail}.npy"), idx.astype(np.float64))
 
 
 def self_launch(args):
@@ -456,14 +490,16 @@ def main():
         # takes it tens of milliseconds of load to get there: the driver's --steps 20 window (13 ms at
         # round 4's 16-frame steps) measured cold read ~13 % low (profiles/r04_clock/).  So the window is measured once
         # cold (reported as cold_window), then the integrate runs untimed for preheat_ms, the
-        # volume is reset, and the W warm-up and K timed steps run as always.
-        run_timed(vol, depth, rgb, K, Tinv, 0, Wf, F, sync, barrier, False)
-        cdt = max_over_ranks(run_timed(vol, depth, rgb, K, Tinv, Wf, Kf, F, sync, barrier, not args.no_profile))
-        cst = vol.stats()
-        cold = {"frames_per_s": round(Kf / cdt, 1),
-                "kernel_avg_us": round(1e3 * cst["kernel_ms"] / max(1, cst["kernel_launches"]), 2),
-                "note": f"the same window on a fresh volume before the clock warm-up ({args.preheat_ms:.0f} ms of "
-                        f"untimed integrate launches, then a reset)"}
+        # volume is reset, and the W warm-up and K timed steps run as always.  (The cold reading
+        # is a measurement of its own: --full.)
+        if args.full:
+            run_timed(vol, depth, rgb, K, Tinv, 0, Wf, F, sync, barrier, False)
+            cdt = max_over_ranks(run_timed(vol, depth, rgb, K, Tinv, Wf, Kf, F, sync, barrier, not args.no_profile))
+            cst = vol.stats()
+            cold = {"frames_per_s": round(Kf / cdt, 1),
+                    "kernel_avg_us": round(1e3 * cst["kernel_ms"] / max(1, cst["kernel_launches"]), 2),
+                    "note": f"the same window on a fresh volume before the clock warm-up ({args.preheat_ms:.0f} ms of "
+                            f"untimed integrate launches, then a reset)"}
         t_end = time.perf_counter() + args.preheat_ms / 1e3
         f0 = Wf + Kf
         while time.perf_counter() < t_end:
@@ -475,6 +511,10 @@ def main():
     first_timed = LAUNCHES["issued"] + 2  # (the timed call's first two launches fill the pipeline)
     dt = run_timed(vol, depth, rgb, K, Tinv, Wf, Kf, F, sync, barrier, not args.no_profile)
     st = vol.stats()
+    if args.dump_outputs:  # before any side leg integrates further into the volume
+        t0 = time.perf_counter()
+        dump_outputs(vol, args.dump_outputs, rank, n)
+        log(f"[rank {rank}] wrote the sampled volume to {args.dump_outputs} in {time.perf_counter() - t0:.1f}s")
     dt_max = max_over_ranks(dt)
     vox = sum_over_ranks(float(st["voxel_updates"]))
     fps = Kf / dt_max
@@ -738,7 +778,7 @@ def main():
     if rank == 0:
         line = {
             "metric": "depth frames/sec (640x480 into 512^3 @ 2 cm dense TSDF; hash alongside)",
-            "value": round(fps, 1), "unit": "frames/s", "n_gpus": n, "steps": Ks, "warmup": W,
+            "value": round(fps, 1), "unit": "frames/s", "n_gpus": n, "steps": Ks, "warmup": W, "full": args.full,
             "ms_per_step": round(1e3 * dt_max / Ks, 4), "frames_per_step": BATCH,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
             "build_id": _ffi.build_id(),

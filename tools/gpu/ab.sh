@@ -17,7 +17,7 @@ for rep in $(seq 1 $reps); do
       *) export TSDF_HIP_LIB=$PWD/abtest/lib$name.so ;;
     esac
     tag=${name//=/_}; tag=${tag//+/_}
-    env "${envs[@]}" timeout -k 10 300 python bench.py --no-cpu --no-mesh --no-ingest --no-dropin > $O/$tag.$rep.json 2> $O/$tag.$rep.err || exit $?
+    env "${envs[@]}" timeout -k 10 300 python bench.py --full --no-cpu --no-mesh --no-ingest --no-dropin > $O/$tag.$rep.json 2> $O/$tag.$rep.err || exit $?
     env "${envs[@]}" timeout -k 10 200 python tools/scaling_sim.py --only 8:0 --steps 1000 --warmup 50 > $O/s8_$tag.$rep.json 2> $O/s8_$tag.$rep.err || exit $?
     env "${envs[@]}" timeout -k 10 200 python tools/scaling_sim.py --hash --only 8:0 --steps 400 > $O/h8_$tag.$rep.json 2> $O/h8_$tag.$rep.err || exit $?
     echo "$tag $rep $(python -c "import json;d=json.load(open('$O/$tag.$rep.json'));print(d['value'],d['hash']['frames_per_s'])") s8 $(python -c "import json;print(json.load(open('$O/s8_$tag.$rep.json'))['fps'])") $(python -c "import json;print(json.load(open('$O/h8_$tag.$rep.json'))['hash8']['fps'])")" >> $O/summary.txt

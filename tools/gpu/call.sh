@@ -10,8 +10,8 @@
 #                      anything else = abtest/lib<name>.so
 #   abs:<reps>:<a,b,..> tools/gpu/ab.sh: the bench and rank 0 of eighth dense / hash shards, per build
 #                      ("base", abtest/lib<name>.so, or VAR=VAL[+VAR2=VAL2] on the in-tree library)
-#   bench[@tag][:<args>]  bench.py --gpus 1 --steps 20 --warmup 5 [args, '+'-separated] -> bench[_tag].json
-#   gloo2[:<args>]     bench.py --gpus 2 --dist-backend gloo (two ranks on the one GPU) -> bench_gpus2_gloo.json
+#   bench[@tag][:<args>]  bench.py --gpus 1 --steps 20 --warmup 5 --full [args, '+'-separated] -> bench[_tag].json
+#   gloo2[:<args>]     bench.py --gpus 2 --full --dist-backend gloo (two ranks on the one GPU) -> bench_gpus2_gloo.json
 #   sq[:<lib>]         one rocprofv3 --pmc SQ pass over the dense + hash bench legs
 #   prof               the round profile (tools/gpu/run_round_prof.sh)
 #   py:<script>[:args] python tools/gpu/<script> [args, '+'-separated]
@@ -73,7 +73,7 @@ for step in "$@"; do
     gloo2*)
       # gloo2[:args]: the bench's multi-rank path, two ranks sharing the one GPU over gloo
       args=""; [[ $step == *:* ]] && args=${step#*:}; args=${args//+/ }
-      timeout -k 10 600 python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 $args \
+      timeout -k 10 600 python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --full $args \
         > "$O/bench_gpus2_gloo.json" 2> "$O/bench_gpus2_gloo.err" || exit 1
       ;;
     bench*)
@@ -81,7 +81,7 @@ for step in "$@"; do
       head=${step%%:*}; tag=${head#bench}; tag=${tag#@}
       args=""; [[ $step == *:* ]] && args=${step#*:}; args=${args//+/ }
       out="$O/bench${tag:+_$tag}"
-      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 $args > "$out.json" 2> "$out.err" || exit 1
+      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full $args > "$out.json" 2> "$out.err" || exit 1
       ;;
     sq*)
       l=${step#sq}; l=${l#:}
@@ -89,7 +89,7 @@ for step in "$@"; do
       TSDF_HIP_LIB=$(lib "$l") timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY \
         SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VMEM GRBM_GUI_ACTIVE GRBM_COUNT \
         --kernel-trace --output-format csv -d /tmp/sq_$l -o pmc -- python "$R/bench.py" --gpus 1 --steps 20 --warmup 5 \
-        --no-cpu --no-profile --no-ingest --no-mesh --no-dropin --no-lounge > "$R/$O/sq_$l.json" 2> "$R/$O/sq_$l.err" || exit 1
+        --full --no-cpu --no-profile --no-ingest --no-mesh --no-dropin --no-lounge > "$R/$O/sq_$l.json" 2> "$R/$O/sq_$l.err" || exit 1
       f=$(find /tmp/sq_$l -name "*counter_collection.csv" | head -1)
       [ -n "$f" ] && grep -E "k_fused|Counter_Name" "$f" > "$R/$O/sq_$l.csv"
       cd "$R"
