@@ -6,7 +6,9 @@
   * the fast-path boundaries: weights around the 4063 limit of the LDS part of the reciprocal
     table and the 65503 limit of the whole table (kRcpTab / kRcpBig less kMaxBatch + 1 = 33 with
     32-frame launches, csrc/tsdf_device.h; the preloaded ranges also straddle the 4079 / 65519 and
-    4087 / 65527 of -DTSDF_MAX_BATCH=16 and 8) and non-canonical colours, preloaded with set_state;
+    4087 / 65527 of -DTSDF_MAX_BATCH=16 and 8) and non-canonical colours, preloaded with set_state
+    (on the dense two-gather kernels; every other kernel variant's table, IEEE and exact-colour
+    paths are in test_update_paths_gpu.py);
   * config[4] per rank: bucket-range hash shard 5 of 8 over a 1024^3 @ 1 cm extent over its whole
     10,000-frame sequence in one asynchronous call (the table doubles under the 0.75 policy and
     the pool grows mid-run), against dense slabs (and those against the oracle) on rows restricted
