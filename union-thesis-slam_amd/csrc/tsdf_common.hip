@@ -187,6 +187,7 @@ int Base::set_batch(int want) {
     if (const char* e = getenv("TSDF_DEFER_DMA_FRAMES")) dma_grain = atoi(e) < 1 ? 1 : atoi(e);
     if (const char* e = getenv("TSDF_RGB_DIRECT")) rgb_direct = atoi(e) != 0;  // (A/B, parity tests)
     if (const char* e = getenv("TSDF_TEXEL")) texel_mode = atoi(e) != 0;
+    if (const char* e = getenv("TSDF_CULL_WAVES")) cull_waves_mode = std::min(std::max(atoi(e), 0), kFusedWG / 64);
     if (const char* e = getenv("TSDF_DEFER_MM")) defer_mm = atoi(e) != 0;
     if (list_set[0]) return TSDF_OK;
     TSDF_HIP(hipMalloc(&list_set[0], sizeof(ListEntry) * (size_t)n_bricks * batch));

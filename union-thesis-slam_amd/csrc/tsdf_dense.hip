@@ -146,7 +146,10 @@ int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, cons
         const Batch& bp = has_p ? bts[jp % kSets] : kNone;
         Stage sg{};
         sg.gi = has_i ? gi_full : 0;
-        sg.gc = has_c ? gc_full : 0;
+        // the cull in service waves of the integrate workgroups where the launch has both stages
+        // (Base::cull_waves); the fill launch L = -1 keeps the cull workgroups
+        sg.cw = has_i && has_c ? B.cull_waves() : 0;
+        sg.gc = has_c && sg.cw == 0 ? gc_full : 0;
         sg.cg = B.cull_per_wg();
         sg.ptx = (W + 63) / 64;
         sg.pty = (H + 63) / 64;

@@ -118,8 +118,10 @@ constexpr int kFullBatch = TSDF_FULL_BATCH < kMaxBatch ? TSDF_FULL_BATCH : kMaxB
 #endif
 // Per-set list counters (reset by the prep of the batch): word c = entries of cost class c
 // (1..kMaxBatch); words kDoneWord / kDoneWordC = integrate and cull workgroups finished (fused hash
-// launch; the launch counts on its cull's set, or on its integrate's set when it has no cull).
-constexpr int kDoneWord = kMaxBatch + 8, kDoneWordC = kMaxBatch + 9;
+// launch; the launch counts on its cull's set, or on its integrate's set when it has no cull);
+// word kCursorWord = the next cull unit (superbrick) of a dense launch whose integrate waves do
+// the cull (cull_units).
+constexpr int kDoneWord = kMaxBatch + 8, kDoneWordC = kMaxBatch + 9, kCursorWord = kMaxBatch + 10;
 constexpr int kCountWords = kMaxBatch + 16;
 constexpr int kRcpTab = 4096;  // LDS table of RN(1/n), n < kRcpTab (32 KB per workgroup)
 // The whole table in HBM (512 KB, L2-resident) for waves with a weight past the LDS part (long
@@ -1388,6 +1390,58 @@ __device__ inline void cull_superbrick(const Vol& v, const Batch& bt, const Tabl
     flush_stats(s_stat, stats);
 }
 
+// The dense cull done by waves of the integrate workgroups (k_fused with Stage::cw > 0: no cull
+// workgroups, which could only start in the whole slots that finished integrate workgroups free,
+// at the launch's end).  A unit is one superbrick against all frames of the batch, taken by one
+// wave from the launch-wide cursor count[kCursorWord] (zeroed with the set's other words by the
+// batch's prep, one launch earlier): lane = brick as in cull_superbrick, the frame bits kept in a
+// register, then append_kept.  The wave returns when the cursor has run past the last unit; it
+// reads no other wave's result, so nothing waits.  Statistics go to the workgroup's s_stat.
+#ifndef TSDF_CULL_WAVE_PRIO  // issue priority of a wave while it culls (0..3): 3, so the unit ends sooner
+#define TSDF_CULL_WAVE_PRIO 3  // and the wave returns to the integrate (-1.1 % per launch against 0)
+#endif
+#ifndef TSDF_PAIR_SKEW  // the skewed deal's m in launches with service waves (integrate_items; 0: off)
+#define TSDF_PAIR_SKEW 20
+#endif
+#ifndef TSDF_TAIL_PRIO  // issue priority of the dense launch's cull and prep workgroups (0..3)
+#define TSDF_TAIL_PRIO 0
+#endif
+__device__ inline void cull_units(const Vol& v, const Batch& bt, ListEntry* list, unsigned int* count,
+                                  unsigned long long* s_stat) {
+    const int lane = lane_id();
+    const int nsx = (v.nb[0] + (1 << v.sb[0]) - 1) >> v.sb[0];
+    const int nsy = (v.nb[1] + (1 << v.sb[1]) - 1) >> v.sb[1];
+    const int nsz = (v.nb[2] + (1 << v.sb[2]) - 1) >> v.sb[2];
+    const unsigned n_sb = (unsigned)(nsx * nsy * nsz);
+    const int n = __builtin_amdgcn_readfirstlane(bt.n);
+    bool prio = false;
+    for (;;) {
+        unsigned u = 0;
+        if (lane == 0) u = atomicAdd(&count[kCursorWord], 1u);
+        u = __builtin_amdgcn_readfirstlane(u);
+        if (u >= n_sb) break;
+        if (TSDF_CULL_WAVE_PRIO && !prio) {
+            __builtin_amdgcn_s_setprio(TSDF_CULL_WAVE_PRIO);
+            prio = true;
+        }
+        const int si = (int)u;
+        const int lz = lane & ((1 << v.sb[2]) - 1), ly = (lane >> v.sb[2]) & ((1 << v.sb[1]) - 1);
+        const int lx = lane >> (v.sb[1] + v.sb[2]);
+        const int sx = si / (nsy * nsz), sr = si - sx * (nsy * nsz), sy = sr / nsz, sz = sr - sy * nsz;
+        const int bx = (sx << v.sb[0]) + lx, by = (sy << v.sb[1]) + ly, bz = (sz << v.sb[2]) + lz;
+        const bool test = bx < v.nb[0] && by < v.nb[1] && bz < v.nb[2];
+        unsigned fmask = 0;
+#pragma unroll 2
+        for (int f = 0; f < n; ++f) {
+            const Frame& fr = bt.f[f];
+            if (test && cull_brick(v, fr, bt.pg, brick_box(v, fr.eye, bx, by, bz))) fmask |= 1u << f;
+        }
+        append_kept<false>(v, list, count, s_stat, nullptr, (unsigned)(((long long)bx * v.nb[1] + by) * v.nb[2] + bz),
+                           fmask, n);
+    }
+    if (TSDF_CULL_WAVE_PRIO && prio) __builtin_amdgcn_s_setprio(0);
+}
+
 // The cull of a bucket-range hash shard (Table::owned): its bricks are spread over the whole
 // extent (one in n_shards, by home bucket), so instead of walking every superbrick of the extent it
 // walks only the bricks the shard owns, 64 per workgroup (lane = brick, one wave per frame at a
@@ -1464,16 +1518,17 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
                                        const ListEntry* list, unsigned int* count, int n_list, int wave,
                                        int n_waves, unsigned long long* s_stat, const double* s_rcp,
                                        unsigned* s_next, int wg, int n_wg, int* res, unsigned& nupd,
-                                       unsigned& nuniq);
+                                       unsigned& nuniq, int skew);
 template <bool HASH, int DK, int CK, bool OW1, int NZ, bool CU = false>
 __device__ inline void integrate_list(const Vol& v, const Batch& bt, const Pool& pool, const Table& tab,
                                       const ListEntry* list, unsigned int* count, int n_list, int wave,
                                       int n_waves, unsigned long long* s_stat, const double* s_rcp,
-                                      unsigned* s_next = nullptr, int wg = 0, int n_wg = 1, int* res = nullptr) {
+                                      unsigned* s_next = nullptr, int wg = 0, int n_wg = 1, int* res = nullptr,
+                                      int skew = 0) {
     wave = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform: the list walk stays scalar
     unsigned nupd = 0, nuniq = 0;  // the wave's voxel updates over all its items (ST_VOXELS, ST_UNIQUE; wave-uniform)
     integrate_items<HASH, DK, CK, OW1, NZ, CU>(v, bt, pool, tab, list, count, n_list, wave, n_waves, s_stat, s_rcp,
-                                           s_next, wg, n_wg, res, nupd, nuniq);
+                                           s_next, wg, n_wg, res, nupd, nuniq, skew);
     if (lane_id() == 0 && nupd) {
         atomicAdd(&s_stat[ST_VOXELS], (unsigned long long)nupd);
         atomicAdd(&s_stat[ST_UNIQUE], (unsigned long long)nuniq);
@@ -1485,7 +1540,7 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
                                        const ListEntry* list, unsigned int* count, int n_list, int wave,
                                        int n_waves, unsigned long long* s_stat, const double* s_rcp,
                                        unsigned* s_next, int wg, int n_wg, int* res, unsigned& nupd,
-                                       unsigned& nuniq) {
+                                       unsigned& nuniq, int skew) {
     constexpr int parts = 8 / NZ;  // waves per listed brick
     if (!count) {  // a flat list of n_list entries (hash overflow re-run)
         for (int e = wave; e < n_list * parts; e += n_waves)
@@ -1529,7 +1584,22 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
         // brick of the list, spread over the whole image.  Renumbered, workgroup w deals as
         // (w % 8) * n_wg/8 + w / 8: each XCD takes runs of n_wg/8 consecutive bricks (neighbours
         // in the cull's order), whose gathers share its L2.
+        // Skewed deal (skew != 0, m = TSDF_PAIR_SKEW; dense launches whose cull runs in service waves, k_fused): of
+        // the two workgroups of a CU the later-dispatched one always ends last, by ~100 us at 512^3
+        // (the older one wins the issue arbitration), and with no cull workgroups left to take the
+        // freed slot that time is idle.  So a workgroup of the later-dispatched half gives the
+        // brick of every m-th round to its partner in the earlier half (workgroup - n_wg / 2),
+        // which takes it right after its own brick of that round (k still increases per wave).
+        constexpr unsigned skew_m = TSDF_PAIR_SKEW > 1 ? TSDF_PAIR_SKEW : 2;  // (m: a compile-time divisor)
+        const bool skewed = skew != 0 && TSDF_PAIR_SKEW > 1 && (n_wg & 15) == 0;
+        const bool late = wg >= (n_wg >> 1);
+        int wg_late = late ? wg : wg + (n_wg >> 1);
+        if ((n_wg & 7) == 0) wg_late = (wg_late & 7) * (n_wg >> 3) + (wg_late >> 3);
         if ((n_wg & 7) == 0) wg = (wg & 7) * (n_wg >> 3) + (wg >> 3);
+#else
+        constexpr unsigned skew_m = 2;
+        const int wg_late = 0;
+        const bool late = false, skewed = false;
 #endif
         const unsigned mine = total > wg ? (unsigned)((total - wg + n_wg - 1) / n_wg) * parts : 0u;
         const bool use_prio = kPrio && mine >= (HASH ? TSDF_PRIO_MIN_HASH : TSDF_PRIO_MIN);  // (wave-uniform)
@@ -1554,7 +1624,17 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
             // bricks dealt to workgroups (brick k to workgroup k mod n_wg), the parts of one brick
             // taken one after the other, so they run side by side on the workgroup's waves and
             // share their depth / colour gathers in the CU's cache
-            const long long k = (long long)wg + (long long)(j / parts) * n_wg;  // increasing for this wave
+            long long k = (long long)wg + (long long)(j / parts) * n_wg;  // increasing for this wave
+            if (skewed) {
+                const unsigned q = j / parts;  // the workgroup's q-th brick
+                if (late) {  // rounds r with r % m != m - 1
+                    k = (long long)wg + (long long)((q / (skew_m - 1)) * skew_m + q % (skew_m - 1)) * n_wg;
+                } else {  // every round, and the partner's brick of rounds r % m == m - 1
+                    const unsigned g = q / (skew_m + 1), pos = q % (skew_m + 1);
+                    k = pos < skew_m ? (long long)wg + (long long)(g * skew_m + pos) * n_wg
+                                               : (long long)wg_late + (long long)(g * skew_m + skew_m - 1) * n_wg;
+                }
+            }
             if (k >= (long long)total) return false;
             while (c > 0 && (unsigned)k - k0 >= nc) {
                 k0 += nc;
@@ -1834,6 +1914,8 @@ struct Stage {
     unsigned int* count_c;
     unsigned int* count_p;   // prep: count of batch k+2 (reset for its cull)
     int gi, gc;              // integrate / cull workgroups
+    int cw;                  // dense: > 0: the last cw waves of every integrate workgroup start as the
+                             // cull's service waves (cull_units), and gc = 0
     int cg;                  // superbricks per cull workgroup (<= kCullGMax)
     int ptx, pty;            // prep tiles per frame (x, y)
     long long seq;           // hash: launch number for the pool report (Table::rb)
@@ -1881,7 +1963,7 @@ __global__ __launch_bounds__(kFusedWG) __attribute__((amdgpu_waves_per_eu(TSDF_D
     const Table no_table{};
 #ifdef TSDF_WG_TIMES
     // (launches with all three stages only: the steady state of a call)
-    const bool rec = sg.gi > 0 && sg.gc > 0 && (int)gridDim.x > sg.gi + sg.gc && b < kWgTimes;
+    const bool rec = sg.gi > 0 && (sg.gc > 0 || sg.cw > 0) &&(int)gridDim.x > sg.gi + sg.gc && b < kWgTimes;
     if (tid == 0 && rec) g_wg_times[0][b] = __builtin_amdgcn_s_memrealtime();
 #endif
     if (b < sg.gi) {
@@ -1891,15 +1973,25 @@ __global__ __launch_bounds__(kFusedWG) __attribute__((amdgpu_waves_per_eu(TSDF_D
             for (int i = tid; i < kRcpTab / 2; i += kFusedWG) ((double2*)s_buf)[i] = ((const double2*)v.rcp)[i];
         __syncthreads();
         constexpr int wpg = kFusedWG / 64;
+        // service waves: the next batch's cull, until its units run out
+        const int cw = __builtin_amdgcn_readfirstlane(sg.cw);
+        if (cw > 0 && __builtin_amdgcn_readfirstlane(tid >> 6) >= wpg - cw)
+            cull_units(item_vol(v), bc, sg.list_c, sg.count_c, s_stat);
         integrate_list<false, DK, 0, OW1, NZ, CU>(v, bi, pool, no_table, sg.list_i, sg.count_i, 0,
                                              b * wpg + (tid >> 6), sg.gi * wpg, s_stat,
-                                             OW1 ? s_buf : nullptr, &s_next, b, sg.gi);
+                                             OW1 ? s_buf : nullptr, &s_next, b, sg.gi, nullptr,
+                                             cw > 0 ? TSDF_PAIR_SKEW : 0);
+        // (every wave once more, so the cull is complete at the launch's end whatever the service
+        // waves managed: one atomic where the cursor has already run out)
+        if (cw > 0) cull_units(item_vol(v), bc, sg.list_c, sg.count_c, s_stat);
         __syncthreads();
         flush_stats(s_stat, stats);
     } else if (b < sg.gi + sg.gc) {
+        if (TSDF_TAIL_PRIO) __builtin_amdgcn_s_setprio(TSDF_TAIL_PRIO);
         cull_superbrick<false>(v, bc, no_table, sg.list_c, sg.count_c, stats, b - sg.gi, (unsigned*)s_buf,
                                s_stat, nullptr, sg.cg);
     } else {
+        if (TSDF_TAIL_PRIO) __builtin_amdgcn_s_setprio(TSDF_TAIL_PRIO);
         const int t = b - sg.gi - sg.gc, per = sg.ptx * sg.pty;
         const int f = t / per, r = t - f * per;
         float(*sa)[33] = (float(*)[33])s_buf;

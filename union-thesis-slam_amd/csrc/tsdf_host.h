@@ -12,6 +12,10 @@
 #include "tsdf_device.h"
 #include "tsdf_hip.h"
 
+#ifndef TSDF_CULL_WAVES_DEFAULT  // service waves per integrate workgroup where the rule applies (Base::cull_waves)
+#define TSDF_CULL_WAVES_DEFAULT 2
+#endif
+
 namespace tsdf {
 
 int set_error(int code, const char* fmt, ...);
@@ -214,6 +218,24 @@ struct Base {
         return cull_grid() >= 1024 ? 3 : 1;
     }
     unsigned cull_grid_fused() const { return (cull_grid() + cull_per_wg() - 1) / cull_per_wg(); }
+    // Service waves (dense k_fused, cull_units in tsdf_device.h): in a launch with an integrate and
+    // a cull stage, the last cull_waves() waves of every integrate workgroup do the cull before they
+    // join the integrate, and no cull workgroups are dispatched.  Unsharded handles only (shards
+    // keep the cull workgroups: their cull is the launch's tail, one superbrick per workgroup).
+    // By default 2 waves of 12 on whole volumes of >= 4096 superbricks (512^3: -2.4 % per launch,
+    // with 1 the cull outlasts the integrate, +3.7 %; 3 and 4 cost more integrate time than 2).  A
+    // unit takes ~100 us beside a running integrate, so short launches lose: the lounge volume
+    // (1170 superbricks, 205 us per launch) took 292 us with service waves, and keeps the cull
+    // workgroups.  Volumes between the two are not measured (profiles/r07_tail/).
+    // TSDF_CULL_WAVES=n forces n (0: cull workgroups; up to every wave of the workgroup).
+    int cull_waves_mode = -1;  // (-1: by the rule)
+    static constexpr int kCullWavesDefault = TSDF_CULL_WAVES_DEFAULT;
+    static constexpr unsigned kCullWavesMinSb = 4096;
+    int cull_waves() const {
+        if (vol.xstride > kBrickEdge) return 0;
+        if (cull_waves_mode >= 0) return cull_waves_mode;
+        return cull_g <= 0 && cull_grid() >= kCullWavesMinSb ? kCullWavesDefault : 0;
+    }
     int read_stats(tsdf_stats_t* out, int reset);
     // Vol::canon from the first n_vox voxels of the pool (after a set or an import; synchronous)
     int check_canon(long long n_vox);
