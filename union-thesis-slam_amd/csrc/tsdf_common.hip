@@ -43,11 +43,9 @@ PyrLayout pyr_layout(int H, int W) {
 
 // Timing-only events: no system-scope fence when they complete (hip_runtime_api.h documents
 // hipEventDisableSystemFence for exactly this use), so recording them does not add a cache
-// writeback between the kernels they bracket.  TSDF_PROF_EVFLAGS overrides (A/B).
+// writeback between the kernels they bracket.
 static int new_timing_event(hipEvent_t* e) {
-    const char* ef = getenv("TSDF_PROF_EVFLAGS");
-    const unsigned fl = ef ? (unsigned)strtoul(ef, nullptr, 0) : (unsigned)hipEventDisableSystemFence;
-    TSDF_HIP(hipEventCreateWithFlags(e, fl));
+    TSDF_HIP(hipEventCreateWithFlags(e, hipEventDisableSystemFence));
     return TSDF_OK;
 }
 
@@ -134,7 +132,6 @@ int Base::init(int dev, const int64_t dims[3], const int64_t off[3], const float
     if (dev < 0 || dev >= ndev) return set_error(TSDF_E_ARG, "device %d out of range [0,%d)", dev, ndev);
     device = dev;
     TSDF_HIP(hipSetDevice(device));
-    if (const char* e = getenv("TSDF_CULL_G")) cull_g = atoi(e);  // A/B override (Base::cull_per_wg)
     for (int a = 0; a < 3; ++a) {
         const int64_t o = off ? off[a] : 0;
         if (dims[a] <= 0 || o < 0 || dims[a] + o > (1 << 24))

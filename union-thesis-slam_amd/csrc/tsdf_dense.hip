@@ -169,7 +169,7 @@ int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, cons
         hipEvent_t e0 = nullptr;
         if (has_i) TSDF_TRY(B.prof.begin(B.stream, &e0));
         // (u32 colour registers where the volume is canonical: obs_weight 1 and NZ = 4, tsdf_device.h)
-        const bool cu = TSDF_COLOR_U32 && ow1 && h->nz == 4 && B.vol.canon;
+        const bool cu = ow1 && h->nz == 4 && B.vol.canon;
         const int sel = (ow1 ? 1 : 0) | (h->nz == 4 ? 2 : 0) | (dk == TSDF_DEPTH_U16_MM ? 0 : 4) | (cu ? 8 : 0) |
                         (tex ? 16 : 0);
         const FusedArgs args{B.vol, bi, bc, bp, B.pool, B.stats, sg};
@@ -321,7 +321,7 @@ static int dense_create(const int64_t dims[3], const int64_t index_offset[3], in
     if (r == TSDF_OK) {
         // three-stage pipeline launches; TSDF_PIPELINE=0 forces the in-line path
         if (const char* e = getenv("TSDF_PIPELINE")) h->fused = atoi(e) != 0;
-        if (const char* e = getenv("TSDF_FUSED_GI_PER_CU")) h->gi_per_cu = std::max(0, atoi(e));  // A/B override
+        if (const char* e = getenv("TSDF_FUSED_GI_PER_CU")) h->gi_per_cu = std::max(0, atoi(e));  // test knob
     }
     if (r == TSDF_OK) {
         const size_t n = (size_t)h->b.n_bricks * kBrickVox * sizeof(float);

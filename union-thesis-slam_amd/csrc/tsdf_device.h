@@ -105,17 +105,6 @@ static_assert(kMaxBatch == 8 || kMaxBatch == 16 || kMaxBatch == 32, "frames per 
 #define TSDF_FULL_BATCH TSDF_MAX_BATCH
 #endif
 constexpr int kFullBatch = TSDF_FULL_BATCH < kMaxBatch ? TSDF_FULL_BATCH : kMaxBatch;
-// integrate_items / integrate_brick options (A/B builds)
-#ifndef TSDF_XCD_DEAL  // deal list items to workgroups XCD by XCD (integrate_items): dense -1.5 %,
-#define TSDF_XCD_DEAL 1  // hash -1 % per launch, hash eighth shard +3 % (profiles/r04_i/)
-#endif
-// (both measured neutral to -1.2 % at the driver window, profiles/r04_h2/ab.jsonl: off)
-#ifndef TSDF_ITEM_PREFETCH  // take the next item before integrating the current one
-#define TSDF_ITEM_PREFETCH 0
-#endif
-#ifndef TSDF_COLOR_U32  // fused launches on canonical volumes: colours held as u32 (integrate_brick CU;
-#define TSDF_COLOR_U32 1  // round 5: dense -1.5 %, hash -1.5 % time per launch, profiles/r05_ab/)
-#endif
 // Per-set list counters (reset by the prep of the batch): word c = entries of cost class c
 // (1..kMaxBatch); words kDoneWord / kDoneWordC = integrate and cull workgroups finished (fused hash
 // launch; the launch counts on its cull's set, or on its integrate's set when it has no cull);
@@ -596,9 +585,10 @@ __device__ inline double readlane_f64(double x, int l) {
 // go through the phases together (project -> gather depth -> test -> colour -> update) to keep
 // many loads in flight per lane.
 // ---------------------------------------------------------------------------------------------
-// NZ = 8: one wave per brick (lane = (x, y) column, 8 z-steps).  NZ = 4 (dense only): two waves
-// per brick, one per z-half (zoff = 0 or 4) -- twice the waves for small culled lists (sharded
-// volumes), where one brick per wave leaves SIMDs idle, and half the per-lane registers.
+// NZ = 4 (the dense kernels and the fused hash launch): two waves per brick, one per z-half
+// (zoff = 0 or 4) -- twice the waves for small culled lists (sharded volumes), where one brick per
+// wave leaves SIMDs idle, and half the per-lane registers.  NZ = 8 (the hash's in-line kernel;
+// the dense kernels under TSDF_DENSE_NZ=8): one wave per brick (lane = (x, y) column, 8 z-steps).
 
 #ifdef TSDF_DIAG
 // Diagnostic builds only (tools/gpu/diag_pairs.py): how often the integrate's paths run, summed over
@@ -790,7 +780,7 @@ __device__ inline void integrate_brick(const Vol& v, const Batch& bt, const Pool
     const double px = vox_world(v.origin[0], v.vs, v.off[0] + col_gx(v, bx) + (lane >> 3));
     const double py = vox_world(v.origin[1], v.vs, v.off[1] + ly);
     const double pz_l = vox_world(v.origin[2], v.vs, v.off[2] + bz * kBrickEdge + (lane & 7));  // lane k: z = k
-    // z-part waves (NZ = 4, dense): this part's z coordinates read out of the lanes once per item
+    // z-part waves (NZ = 4): this part's z coordinates read out of the lanes once per item
     // (+1.5 %); with NZ = 8 the hash kernel has no registers to spare and reads them per frame
     constexpr int kPz = NZ < 8 ? NZ : 1;
     double pzs[kPz];
@@ -1151,9 +1141,8 @@ constexpr int kCullWG = 512;  // k_cull: 8 waves, wave w culls frames w and w + 
 // The cull's wave then initialises its new blocks -- (1, 0, 0) and no entries, 64 lanes per block --
 // and records them for k_free_unused (a block the batch leaves without an entry is freed at the end
 // of the call).  kResFail: the pool or table is full (the brick goes to the host's exact re-run).
-#ifndef TSDF_CULL_PROBE8  // cull_find_or_insert walks the table 8 slots per dependent load (round 6)
-#define TSDF_CULL_PROBE8 1  // instead of one (0: round 5's lane-serial probe, for A/B)
-#endif
+// cull_find_or_insert walks the table 8 slots per dependent load (round 6: profiles/r06_probe_ab/),
+// one slot per load only where the table has fewer than 8.
 // A block taken from the pool for a key whose probe then ended without inserting it (the table ran
 // out of slots after a lost race): recorded in the inserted list as -2 - block, so k_free_unused
 // returns it to the free list at the end of the call (round-5 advisor: it stayed counted as used).
@@ -1182,7 +1171,6 @@ __device__ inline int cull_find_or_insert(const Vol& v, const Table& t, unsigned
     long long s = ref_hash<true>(bx, by, bz, cap, t.int_bits);
     long long tomb = -1, tomb_n = 0;
     int blk = -1;
-#if TSDF_CULL_PROBE8
     if (cap >= 8) {
         // Eight slots per step: the aligned 64-B group of keys holding slot s (four 16-B loads) and
         // its 32 B of slot values, issued together -- one memory latency per 8 slots instead of one
@@ -1259,8 +1247,8 @@ __device__ inline int cull_find_or_insert(const Vol& v, const Table& t, unsigned
         spare_block(t, blk);
         return kResFail;  // table full (the growth policy keeps it below 31/32)
     }
-#endif
-    for (long long n = 0; n < cap; ++n) {  // one slot per step (tables of < 8 slots; A/B)
+    // one slot per step: tables of fewer than 8 slots (next_pow2(map_size) allows them)
+    for (long long n = 0; n < cap; ++n) {
         const unsigned long long k = coh_load(&keys[s]);
         if (k == key) {
             const int b = coh_load(&vals[s]);
@@ -1402,9 +1390,6 @@ __device__ inline void cull_superbrick(const Vol& v, const Batch& bt, const Tabl
 #endif
 #ifndef TSDF_PAIR_SKEW  // the skewed deal's m in launches with service waves (integrate_items; 0: off)
 #define TSDF_PAIR_SKEW 20
-#endif
-#ifndef TSDF_TAIL_PRIO  // issue priority of the dense launch's cull and prep workgroups (0..3)
-#define TSDF_TAIL_PRIO 0
 #endif
 __device__ inline void cull_units(const Vol& v, const Batch& bt, ListEntry* list, unsigned int* count,
                                   unsigned long long* s_stat) {
@@ -1576,37 +1561,30 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
         // Dense: -2.9 % time per 16-frame launch on one GPU, but +3 % on an eighth shard, so from
         // 64 items per workgroup (profiles/r04_p/).
         constexpr bool kPrio = HASH ? TSDF_PRIO_HASH != 0 : TSDF_PRIO != 0;
-#if TSDF_XCD_DEAL
-        // XCD-aware dealing: the launch's workgroups go to the 8 XCDs round-robin (workgroup w on
-        // XCD (w + r) % 8, the rotation r carried over from the dispatches before: measured from
-        // the workgroups' XCC_ID registers, profiles/r05_shards/), so dealing brick k to workgroup
-        // k mod n_wg would hand each XCD every 8th
-        // brick of the list, spread over the whole image.  Renumbered, workgroup w deals as
-        // (w % 8) * n_wg/8 + w / 8: each XCD takes runs of n_wg/8 consecutive bricks (neighbours
-        // in the cull's order), whose gathers share its L2.
-        // Skewed deal (skew != 0, m = TSDF_PAIR_SKEW; dense launches whose cull runs in service waves, k_fused): of
-        // the two workgroups of a CU the later-dispatched one always ends last, by ~100 us at 512^3
-        // (the older one wins the issue arbitration), and with no cull workgroups left to take the
-        // freed slot that time is idle.  So a workgroup of the later-dispatched half gives the
-        // brick of every m-th round to its partner in the earlier half (workgroup - n_wg / 2),
-        // which takes it right after its own brick of that round (k still increases per wave).
+        // XCD-aware dealing (dense -1.5 %, hash -1 % per launch, profiles/r04_i/): the launch's
+        // workgroups go to the 8 XCDs round-robin (workgroup w on XCD (w + r) % 8, the rotation r
+        // carried over from the dispatches before: measured from the workgroups' XCC_ID
+        // registers, profiles/r05_shards/), so dealing brick k to workgroup k mod n_wg would hand
+        // each XCD every 8th brick of the list, spread over the whole image.  Renumbered,
+        // workgroup w deals as (w % 8) * n_wg/8 + w / 8: each XCD takes runs of n_wg/8
+        // consecutive bricks (neighbours in the cull's order), whose gathers share its L2.
+        // Skewed deal (skew != 0, m = TSDF_PAIR_SKEW; dense launches whose cull runs in service
+        // waves, k_fused): of the two workgroups of a CU the later-dispatched one always ends
+        // last, by ~100 us at 512^3 (the older one wins the issue arbitration), and with no cull
+        // workgroups left to take the freed slot that time is idle.  So a workgroup of the
+        // later-dispatched half gives the brick of every m-th round to its partner in the
+        // earlier half (workgroup - n_wg / 2), which takes it right after its own brick of that
+        // round (k still increases per wave).
         constexpr unsigned skew_m = TSDF_PAIR_SKEW > 1 ? TSDF_PAIR_SKEW : 2;  // (m: a compile-time divisor)
         const bool skewed = skew != 0 && TSDF_PAIR_SKEW > 1 && (n_wg & 15) == 0;
         const bool late = wg >= (n_wg >> 1);
         int wg_late = late ? wg : wg + (n_wg >> 1);
         if ((n_wg & 7) == 0) wg_late = (wg_late & 7) * (n_wg >> 3) + (wg_late >> 3);
         if ((n_wg & 7) == 0) wg = (wg & 7) * (n_wg >> 3) + (wg >> 3);
-#else
-        constexpr unsigned skew_m = 2;
-        const int wg_late = 0;
-        const bool late = false, skewed = false;
-#endif
         const unsigned mine = total > wg ? (unsigned)((total - wg + n_wg - 1) / n_wg) * parts : 0u;
         const bool use_prio = kPrio && mine >= (HASH ? TSDF_PRIO_MIN_HASH : TSDF_PRIO_MIN);  // (wave-uniform)
         [[maybe_unused]] int prio = 3;
         if (use_prio) __builtin_amdgcn_s_setprio(3);
-        // (TSDF_ITEM_PREFETCH: each wave takes its next item, and issues the load of its list
-        // entry, before it integrates the current one -- one item held in reserve per wave)
         const auto take = [&](ListEntry& e, int& zoff) -> bool {
             unsigned j = 0;
             if (lane_id() == 0) j = atomicAdd(s_next, 1u);
@@ -1647,22 +1625,8 @@ __device__ inline void integrate_items(const Vol& v, const Batch& bt, const Pool
         };
         ListEntry e = 0;
         int zoff = 0;
-#if TSDF_ITEM_PREFETCH
-        bool have = take(e, zoff);
-        while (have) {
-            ListEntry en = 0;
-            int zn = 0;
-            const bool more = take(en, zn);
-            // (the parts of a brick stay in one workgroup: the hash's z-halves meet in res)
-            integrate_brick<HASH, DK, CK, OW1, NZ, CU>(item_vol(v), bt, pool, tab, e, zoff, s_stat, s_rcp, nupd, nuniq, res);
-            have = more;
-            e = en;
-            zoff = zn;
-        }
-#else
         while (take(e, zoff))  // (the parts of a brick stay in one workgroup: the hash's z-halves meet in res)
             integrate_brick<HASH, DK, CK, OW1, NZ, CU>(item_vol(v), bt, pool, tab, e, zoff, s_stat, s_rcp, nupd, nuniq, res);
-#endif
         if (use_prio) __builtin_amdgcn_s_setprio(0);
         return;
     }
@@ -1987,11 +1951,9 @@ __global__ __launch_bounds__(kFusedWG) __attribute__((amdgpu_waves_per_eu(TSDF_D
         __syncthreads();
         flush_stats(s_stat, stats);
     } else if (b < sg.gi + sg.gc) {
-        if (TSDF_TAIL_PRIO) __builtin_amdgcn_s_setprio(TSDF_TAIL_PRIO);
         cull_superbrick<false>(v, bc, no_table, sg.list_c, sg.count_c, stats, b - sg.gi, (unsigned*)s_buf,
                                s_stat, nullptr, sg.cg);
     } else {
-        if (TSDF_TAIL_PRIO) __builtin_amdgcn_s_setprio(TSDF_TAIL_PRIO);
         const int t = b - sg.gi - sg.gc, per = sg.ptx * sg.pty;
         const int f = t / per, r = t - f * per;
         float(*sa)[33] = (float(*)[33])s_buf;

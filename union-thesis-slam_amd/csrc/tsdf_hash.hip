@@ -1096,7 +1096,7 @@ int hash_run_fused(tsdf_hash* h, int n_frames, const void* depth, int dk, const 
         const FusedHashArgs args{B.vol, bi, bc, bp, B.pool, h->t, B.stats, sg};
         TSDF_HOST_TIME(3);
         // (u32 colour registers where the table's blocks are canonical, tsdf_device.h)
-        const bool cu = TSDF_COLOR_U32 && B.vol.canon;
+        const bool cu = B.vol.canon;
         if (tex) {
             if (cu) hipLaunchKernelGGL((k_fused_hash<2, true>), dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
             else hipLaunchKernelGGL(k_fused_hash<2>, dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
