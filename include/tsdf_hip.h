@@ -59,6 +59,9 @@ extern "C" {
                                and its skipped bricks re-run at the next call, before anything
                                else runs (exact, as for synchronous calls) */
 
+#define TSDF_RAY_REFLAG 16  /* tsdf_*_raycast: recompute the live-brick bits even though the handle's
+                               state has not changed since they were computed (timing tools) */
+
 typedef struct tsdf_dense tsdf_dense_t;
 typedef struct tsdf_hash tsdf_hash_t;
 
@@ -189,6 +192,32 @@ int tsdf_dense_get_rows(tsdf_dense_t* h, const int64_t* rows, int64_t n_rows, fl
  * corners differing in bit e / 4 of the corner index, its lower corner's other two bits being
  * e % 4 in increasing bit order), ntri[256] triangles per case.  Host-only; no device needed. */
 int tsdf_mc_table(int8_t* tri, uint8_t* ntri);
+/* Raycast of the fused model (not in the reference): what the volume looks like from
+ * cam_pose (camera-to-world, row-major 4x4 f64, as integrate() takes it) through K, for an image of
+ * height x width pixels (the image limits of tsdf_dense_integrate).  Along the ray of pixel (u, v)
+ * the samples k = 0, 1, ... lie at camera depth z_k = z_near + k * z_step <= z_far, at the world
+ * point cam_pose * ((u - cx) / fx * z_k, (v - cy) / fy * z_k, z_k).  A sample is valid when the 8
+ * voxels around it (voxel centres at integer indices of the GLOBAL lattice) are inside this handle's
+ * volume and all have weight > 0; its value f is their trilinear tsdf.  The first k >= 1 that is
+ * valid with f_k < 0 decides the ray: a hit when sample k - 1 is valid with f_{k-1} > 0, else a miss
+ * (surface met from behind or from unseen space); no such k is a miss.  For a hit
+ *   depth   H x W f32: z_{k-1} + z_step * f_{k-1} / (f_{k-1} - f_k), metres along the camera z axis
+ *           (a depth image, as integrate() reads it);
+ *   normals H x W x 3 f32: unit gradient of the trilinear interpolant in the cell of the hit point,
+ *           world axes, towards positive tsdf; 0 if that cell is not valid;
+ *   colors  H x W x 3 u8: r, g, b of the voxel nearest the hit point (the rule of the mesh vertices);
+ * a miss writes 0 everywhere.  Any output pointer may be NULL.  Host pointers, or device pointers
+ * with TSDF_DEVICE_PTRS (then TSDF_ASYNC leaves the result to the handle's stream).  Deferred frames
+ * run first; the call follows the launches in flight on the handle's stream.  Space is skipped by
+ * one live bit per brick, recomputed only after a call that changed the state; the result is that
+ * of evaluating every sample (TSDF_RAY_SKIP=0 in the environment at create does exactly that).
+ * The arithmetic is fixed (per-ray setup in f64 rounded once to f32, the march in f32) and restated
+ * by tests/raycast_ref.py.  TSDF_E_ARG: z_step <= 0, z_far < z_near, z_near < 0, more than 2^22
+ * samples per ray, a bad image size, a cyclic column shard.  Slab shards (index_offset) raycast
+ * their own voxels. */
+int tsdf_dense_raycast(tsdf_dense_t* h, int height, int width, const double K[9],
+                       const double cam_pose[16], double z_near, double z_far, double z_step,
+                       float* depth, float* normals, uint8_t* colors, int flags);
 int tsdf_dense_stats(tsdf_dense_t* h, tsdf_stats_t* out, int reset);
 int tsdf_dense_set_profiling(tsdf_dense_t* h, int on);
 
@@ -250,6 +279,17 @@ int tsdf_hash_get_dense(tsdf_hash_t* h, float* tsdf, float* weight, float* color
  * first): get_mesh / get_point_cloud of the hash (hash_fusion.py:465-507) then run the dense
  * handle's marching cubes without a host round trip of the volume. */
 int tsdf_hash_to_dense(tsdf_hash_t* h, tsdf_dense_t* d);
+/* tsdf_dense_raycast on the table: a voxel without an entry has weight 0, as in get_volume.  Absent
+ * blocks are skipped by the table alone; each ray keeps the pool blocks of its current 2x2x2 block
+ * neighbourhood, so the corner fetches probe only when it leaves that neighbourhood.  The same
+ * results as the raycast of the densified volume.  TSDF_E_ARG also for a shard (n_shards > 1). */
+int tsdf_hash_raycast(tsdf_hash_t* h, int height, int width, const double K[9],
+                      const double cam_pose[16], double z_near, double z_far, double z_step,
+                      float* depth, float* normals, uint8_t* colors, int flags);
+/* HIP-event times, in milliseconds, of the calling thread's last raycast that synchronised before
+ * returning on a handle with profiling on (tsdf_*_set_profiling): the live-bit pass (about 0 when
+ * the bits were current) and the march.  -1 before any such call. */
+int tsdf_raycast_last_ms(double* live_ms, double* march_ms);
 int tsdf_hash_sync(tsdf_hash_t* h);
 /* sync, then a pool on mapped memory hands the memory above its live blocks back (pool_capacity
  * = live blocks + ~3 %, in whole 8 MB pieces; the live blocks move into fresh mapped ranges by one

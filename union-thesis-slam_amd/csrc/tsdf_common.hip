@@ -186,6 +186,7 @@ int Base::set_batch(int want) {
     if (const char* e = getenv("TSDF_TEXEL")) texel_mode = atoi(e) != 0;
     if (const char* e = getenv("TSDF_CULL_WAVES")) cull_waves_mode = std::min(std::max(atoi(e), 0), kFusedWG / 64);
     if (const char* e = getenv("TSDF_DEFER_MM")) defer_mm = atoi(e) != 0;
+    if (const char* e = getenv("TSDF_RAY_SKIP")) ray_skip = atoi(e) != 0;  // (0: brute force, tests)
     if (list_set[0]) return TSDF_OK;
     TSDF_HIP(hipMalloc(&list_set[0], sizeof(ListEntry) * (size_t)n_bricks * batch));
     TSDF_HIP(hipMalloc(&count_set[0], sizeof(unsigned int) * kCountWords));
@@ -781,6 +782,15 @@ void Base::release() {
     n_sets = 1;
     if (rcp) (void)hipFree(rcp);
     rcp = nullptr;
+    if (ray_live) (void)hipFree(ray_live);
+    ray_live = nullptr;
+    ray_live_words = 0;
+    ray_live_gen = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (ray_out[k]) (void)hipFree(ray_out[k]);
+        ray_out[k] = nullptr;
+        ray_out_bytes[k] = 0;
+    }
     if (stats) (void)hipFree(stats);
     if (cstream) (void)hipStreamSynchronize(cstream);
     for (int k = 0; k < kSlots; ++k) {

@@ -216,6 +216,7 @@ int dense_run(tsdf_dense* h, int n_frames, const void* depth, int dk, const void
                           frame_bytes_color(ck, H, W) * n_frames, flags));
     CallGuard guard(B, flags);
     B.note_frames(ck, ow, n_frames, 1.0);
+    B.touch_state();
     // the fused pipeline needs the vectorised prep: u16 or f64 depth + RGB8, W % 4 == 0 and
     // (device frames) 8-byte u16 / 16-byte f64 depth and 4-byte colour alignment of every frame
     // (host frames are staged aligned)
@@ -250,6 +251,7 @@ int dense_xfer(tsdf_dense* h, float* tsdf_, float* weight_, float* color_, bool 
     Base& B = h->b;
     TSDF_TRY(dense_flush(h));
     TSDF_HIP(hipSetDevice(B.device));
+    if (!get) B.touch_state();
     const size_t yz = (size_t)B.vol.dims[1] * B.vol.dims[2];
     const long long X = B.vol.dims[0];
     const long long chunk = std::max<long long>(1, std::min<long long>(X, (64ll << 20) / (long long)(yz * sizeof(float))));
@@ -296,6 +298,18 @@ struct DevPtrs {
 }  // namespace
 
 Base* tsdf::dense_base(tsdf_dense_t* d) { return &d->b; }
+
+int tsdf::dense_ray_source(tsdf_dense_t* h, RaySource* out) {
+    Base& B = h->b;
+    TSDF_HIP(hipSetDevice(B.device));
+    if (B.vol.xstride != kBrickEdge || B.vol.xodd != kBrickEdge)
+        return set_error(TSDF_E_ARG, "a cyclic column shard holds no contiguous volume to raycast "
+                                     "(gather it, or shard by slabs)");
+    TSDF_TRY(dense_flush(h));
+    out->b = &B;
+    out->table = nullptr;
+    return TSDF_OK;
+}
 
 extern "C" {
 
@@ -392,6 +406,7 @@ int tsdf_dense_reset(tsdf_dense_t* h) {
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     Base& B = h->b;
     B.dfr.n = 0;  // deferred frames are dropped with the state
+    B.touch_state();
     TSDF_HIP(hipSetDevice(B.device));
     hipLaunchKernelGGL(k_fill3, dim3(4096), dim3(256), 0, B.stream, B.pool.tsdf, B.pool.weight,
                        B.pool.color, (size_t)B.n_bricks * kBrickVox);

@@ -648,6 +648,7 @@ long long pool_target(const tsdf_hash* h, long long need) {
 
 int grow_pool(tsdf_hash* h, long long new_max) {
     Base& B = h->b;
+    B.touch_state();  // (the raycast's live bits are sized by the pool)
     Table& t = h->t;
     // the volume has n_bricks bricks: a pool never needs more blocks than that
     new_max = std::min<long long>(new_max, B.n_bricks);
@@ -704,6 +705,7 @@ int grow_pool(tsdf_hash* h, long long new_max) {
 // pieces: see VArray::grow.  One device copy of the live state (~1.1 GB at 512^3: ~0.5 ms).
 // Nothing changes when the new ranges cannot be had.
 int trim_pool(tsdf_hash* h) {
+    h->b.touch_state();  // (the live blocks move: pool indices change)
     if (!h->vmm) return TSDF_OK;
     TSDF_TRY(read_state(h));
     const long long top = h->host_st.pool_top;
@@ -742,6 +744,7 @@ int trim_pool(tsdf_hash* h) {
 
 int resize_table(tsdf_hash* h, long long new_cap) {
     Base& B = h->b;
+    B.touch_state();
     Table nt = h->t;
     nt.capacity = new_cap;
     DevBufs fresh;
@@ -952,6 +955,7 @@ void launch_integrate(tsdf_hash* h, const Batch& bt, int dk, int ck, const ListE
 // were not touched by any of its frames), then keep the reference's load-factor policy.
 int hash_after_batch(tsdf_hash* h, const Batch& bt, int dk, int ck) {
     Base& B = h->b;
+    B.touch_state();  // (the re-run of skipped bricks)
     TSDF_TRY(read_state(h));
     for (int round = 0; h->host_st.n_overflow > 0 && round < 40; ++round) {
         const long long n_ov = h->host_st.n_overflow;
@@ -1139,6 +1143,7 @@ int hash_run(tsdf_hash* h, int n_frames, const void* depth, int dk, const void* 
              int H, int W, const double* K, const double* Tinv, int flags) {
     Base& B = h->b;
     TSDF_HIP(hipSetDevice(B.device));
+    B.touch_state();
     const unsigned cull_grid = h->t.owned ? (unsigned)std::max(1, (h->t.n_owned + 63) / 64) : B.cull_grid();
     const bool sync = !(flags & TSDF_ASYNC);
     if (!sync && h->rb_used < 0 && n_frames > B.batch && B.prestaged < 0) {
@@ -1314,6 +1319,18 @@ std::vector<unsigned long long> unique_blocks(const Vol& v, const int64_t* ijk, 
 
 }  // namespace
 
+int tsdf::hash_ray_source(tsdf_hash_t* h, RaySource* out) {
+    Base& B = h->b;
+    TSDF_HIP(hipSetDevice(B.device));
+    if (B.vol.n_shards > 1 || h->t.owned)
+        return set_error(TSDF_E_ARG, "a hash shard (%d of %d) holds only its bucket range: merge the shards' "
+                                     "blocks into one table to raycast", B.vol.shard, B.vol.n_shards);
+    TSDF_TRY(hash_flush(h));
+    out->b = &B;
+    out->table = &h->t;
+    return TSDF_OK;
+}
+
 extern "C" {
 
 int tsdf_hash_create(const int64_t dims[3], const float origin[3], double voxel_size, double trunc,
@@ -1439,6 +1456,7 @@ int tsdf_hash_reset(tsdf_hash_t* h) {
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     Base& B = h->b;
     B.dfr.n = 0;  // deferred frames are dropped with the state
+    B.touch_state();
     h->pend.on = false;
     TSDF_HIP(hipSetDevice(B.device));
     hipLaunchKernelGGL(k_fill_keys, dim3(2048), dim3(256), 0, B.stream, h->t.keys, h->t.vals,
@@ -1530,6 +1548,7 @@ int tsdf_hash_insert(tsdf_hash_t* h, const int64_t* ijk, int64_t n, const float*
     if (!h || n < 0 || (n > 0 && !ijk)) return set_error(TSDF_E_ARG, "bad arguments");
     if (n == 0) return TSDF_OK;
     Base& B = h->b;
+    B.touch_state();
     const Vol& v = B.vol;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t x = ijk[3 * i], y = ijk[3 * i + 1], z = ijk[3 * i + 2];
@@ -1580,6 +1599,7 @@ int tsdf_hash_remove(tsdf_hash_t* h, const int64_t* ijk, int64_t n, uint8_t* rem
     if (!h || n < 0 || (n > 0 && !ijk)) return set_error(TSDF_E_ARG, "bad arguments");
     if (n == 0) return TSDF_OK;
     Base& B = h->b;
+    B.touch_state();
     TSDF_HIP(hipSetDevice(B.device));
     TSDF_TRY(hash_flush(h));
     std::vector<unsigned long long> keys = unique_blocks(B.vol, ijk, n);
@@ -1685,6 +1705,7 @@ int tsdf_hash_to_dense(tsdf_hash_t* h, tsdf_dense_t* d) {
     hipLaunchKernelGGL(k_to_bricks, dim3(4096), dim3(256), 0, B.stream, B.vol, h->t, B.pool, D.pool);
     TSDF_HIP(hipGetLastError());
     TSDF_HIP(hipStreamSynchronize(B.stream));
+    D.touch_state();
     D.vol.canon = B.vol.canon;
     return TSDF_OK;
 }
@@ -1775,6 +1796,7 @@ int tsdf_hash_import_blocks(tsdf_hash_t* h, const int32_t* bxyz, int64_t n_block
                             const float* weight_, const float* color_, const uint64_t* occ, int flags) {
     if (!h || n_blocks < 0 || (n_blocks > 0 && !bxyz)) return set_error(TSDF_E_ARG, "bad arguments");
     Base& B = h->b;
+    B.touch_state();
     TSDF_HIP(hipSetDevice(B.device));
     TSDF_TRY(hash_flush(h));
     if (n_blocks == 0) return TSDF_OK;

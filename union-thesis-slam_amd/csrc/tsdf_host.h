@@ -232,6 +232,20 @@ struct Base {
         if (cull_waves_mode >= 0) return cull_waves_mode;
         return cull_grid() >= kCullWavesMinSb ? kCullWavesDefault : 0;
     }
+    // Raycast (tsdf_raycast.hip).  state_gen counts the calls that may have changed
+    // the stored state since create (every integrate path, set, reset, a densify into the handle;
+    // hash: entry insert / remove, block import, pool growth / trim and table rebuilds as well);
+    // the raycast's live bits (one per brick, or per pool block of the hash) are recomputed only
+    // when they were computed for another generation.  TSDF_RAY_SKIP=0: the marcher evaluates
+    // every sample (the brute-force restatement the skip is tested against).
+    unsigned long long state_gen = 1;
+    void touch_state() { ++state_gen; }
+    unsigned* ray_live = nullptr;
+    size_t ray_live_words = 0;
+    unsigned long long ray_live_gen = 0;
+    bool ray_skip = true;
+    void* ray_out[3] = {};  // device buffers of host-pointer raycasts (depth, normals, colours), grown on demand
+    size_t ray_out_bytes[3] = {};
     int read_stats(tsdf_stats_t* out, int reset);
     // Vol::canon from the first n_vox voxels of the pool (after a set or an import; synchronous)
     int check_canon(long long n_vox);
@@ -271,6 +285,15 @@ int copy_mesh(Base& B, const Mesh& m, float* verts, float* normals, uint8_t* col
 
 // The state of a dense handle (tsdf_dense.hip), for the hash's densify into it.
 Base* dense_base(tsdf_dense_t* d);
+
+// What a raycast reads (tsdf_raycast.hip).  The *_ray_source calls run the handle's deferred
+// frames first and refuse the handles a raycast does not serve (cyclic column shards, hash shards).
+struct RaySource {
+    Base* b = nullptr;
+    const Table* table = nullptr;  // the hash's block table; nullptr: dense
+};
+int dense_ray_source(tsdf_dense_t* h, RaySource* out);
+int hash_ray_source(tsdf_hash_t* h, RaySource* out);
 
 // end_call on every exit path of an integrate call (error returns included).
 struct CallGuard {

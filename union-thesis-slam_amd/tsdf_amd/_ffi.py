@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("TSDF_HIP_LIB") or os.path.join(_HERE, "lib", "libtsdf
 
 DEPTH_U16_MM, DEPTH_F64_M = 0, 1
 COLOR_RGB8, COLOR_F32 = 0, 1
-DEVICE_PTRS, ASYNC, DEPTH_INVALID_65535, DEFER = 1, 2, 4, 8
+DEVICE_PTRS, ASYNC, DEPTH_INVALID_65535, DEFER, RAY_REFLAG = 1, 2, 4, 8, 16
 
 E_ARG, E_HIP, E_NODEV, E_CAPACITY, E_OOM = -1, -2, -3, -4, -5
 
@@ -108,6 +108,9 @@ SIGNATURES = {
     "tsdf_hash_stats": [_P, _P, _I],
     "tsdf_hash_set_profiling": [_P, _I],
     "tsdf_hash_keys": [_P, _I64, _I64, _I, _P, _I],
+    "tsdf_dense_raycast": [_P, _I, _I, _P, _P, _D, _D, _D, _P, _P, _P, _I],
+    "tsdf_hash_raycast": [_P, _I, _I, _P, _P, _D, _D, _D, _P, _P, _P, _I],
+    "tsdf_raycast_last_ms": [_P, _P],
 }
 
 _lib = None

@@ -77,6 +77,45 @@ def frame_stack(depth, depth_kind, color, color_kind, device_ptrs):
     return depth, dk, color, ck
 
 
+def raycast_call(fn, handle, device, vol_bnds, voxel_size, cam_intr, cam_pose, hw, z_near, z_far, z_step,
+                 normals, colors, out):
+    """The raycast entry points' host side (tsdf_dense_raycast / tsdf_hash_raycast): defaults,
+    output arrays (numpy) or CUDA tensors filled in place."""
+    H, W = int(hw[0]), int(hw[1])
+    pose = _ffi.f64(cam_pose, 16)
+    if z_step is None:
+        z_step = float(voxel_size)
+    if z_far is None:  # the largest camera z of the volume's 8 corners
+        b = np.asarray(vol_bnds, dtype=np.float64)
+        corners = np.array([[b[0, i], b[1, j], b[2, k], 1.0] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+        z_far = float(max((np.linalg.inv(pose.reshape(4, 4)) @ corners.T)[2].max(), float(z_near)))
+    K = _ffi.f64(cam_intr, 9)
+    if out is not None:  # (out decides the fields: a None entry is not computed; normals / colors are not consulted)
+        import torch
+        if len(out) != 3:
+            raise ValueError("out takes (depth, normals, colors) tensors or None entries")
+        want = (("depth", (H, W), torch.float32), ("normals", (H, W, 3), torch.float32),
+                ("colors", (H, W, 3), torch.uint8))
+        for o, (name, shape, dtype) in zip(out, want):
+            if o is None:
+                continue
+            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == dtype and tuple(o.shape) == shape
+                    and o.is_contiguous()):
+                raise ValueError(f"out {name} must be a contiguous CUDA tensor of shape {shape} and dtype {dtype}")
+            if o.device.index != device:
+                raise ValueError(f"out {name} lives on {o.device}, the handle on device {device}")
+        ptrs = [None if o is None else o.data_ptr() for o in out]
+        _ffi.call(fn, handle, H, W, _ffi.ptr(K), _ffi.ptr(pose), float(z_near), float(z_far), float(z_step),
+                  *ptrs, _ffi.DEVICE_PTRS)
+        return out
+    d = np.empty((H, W), np.float32)
+    n = np.empty((H, W, 3), np.float32) if normals else None
+    c = np.empty((H, W, 3), np.uint8) if colors else None
+    _ffi.call(fn, handle, H, W, _ffi.ptr(K), _ffi.ptr(pose), float(z_near), float(z_far), float(z_step),
+              _ffi.ptr(d), _ffi.ptr(n), _ffi.ptr(c), 0)
+    return d, n, c
+
+
 class TSDFVolume:
     """Volumetric TSDF Fusion of RGB-D Images, on an MI355X.
 
@@ -268,6 +307,19 @@ class TSDFVolume:
         _ffi.call("tsdf_dense_get_rows", self._h, _ffi.ptr(rows), len(rows), _ffi.ptr(t), _ffi.ptr(w),
                   _ffi.ptr(c), 0)
         return t, w, c
+
+    def raycast(self, cam_intr, cam_pose, hw, *, z_near=0.0, z_far=None, z_step=None, normals=True,
+                colors=True, out=None):
+        """The fused model seen from cam_pose (camera-to-world) through cam_intr, as an image of
+        hw = (H, W) pixels (tsdf_dense_raycast): (depth (H,W) f32 metres along the
+        camera z axis, normals (H,W,3) f32 unit, colors (H,W,3) u8); 0 where the ray misses.  A
+        field not asked for is None.  z_step defaults to the voxel size, z_far to the largest
+        camera z of the volume's corners.  out = (depth, normals, colors) contiguous CUDA tensors
+        of those shapes and dtypes on the handle's device (or None entries: that field is not
+        computed) are filled on the device instead (no host copy) and returned; `normals` /
+        `colors` are not consulted then.  Anything else in out raises ValueError."""
+        return raycast_call("tsdf_dense_raycast", self._h, self.device, self._vol_bnds, self._voxel_size, cam_intr,
+                            cam_pose, hw, z_near, z_far, z_step, normals, colors, out)
 
     def get_point_cloud(self):
         """grid_fusion.py:322-338: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""

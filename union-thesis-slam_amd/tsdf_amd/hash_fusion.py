@@ -292,6 +292,13 @@ class HashTable:
         _ffi.call("tsdf_hash_to_dense", self._h, vol._h)
         return vol
 
+    def raycast(self, cam_intr, cam_pose, hw, *, z_near=0.0, z_far=None, z_step=None, normals=True,
+                colors=True, out=None):
+        """As TSDFVolume.raycast, on the table (tsdf_hash_raycast): the raycast of get_volume()'s
+        densified volume, without densifying."""
+        return grid_fusion.raycast_call("tsdf_hash_raycast", self._h, self.device, self._vol_bounds, self._voxel_size,
+                                        cam_intr, cam_pose, hw, z_near, z_far, z_step, normals, colors, out)
+
     def get_mesh(self):
         """hash_fusion.py:465-484: marching cubes of the densified volume, on the device."""
         return self._as_grid().get_mesh()
