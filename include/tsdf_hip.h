@@ -65,6 +65,35 @@ extern "C" {
 typedef struct tsdf_dense tsdf_dense_t;
 typedef struct tsdf_hash tsdf_hash_t;
 
+/* ---- tracking ------------------------------------------------------------- */
+#define TSDF_ICP_MAX_ITER 64    /* the cap on tsdf_icp_params_t.max_iter */
+#define TSDF_TRACK_CONVERGED 1  /* an update had |w| <= eps_rot and |t| <= eps_trans */
+#define TSDF_TRACK_MAX_ITER 2   /* max_iter updates were applied and none was that small */
+#define TSDF_TRACK_LOST 3       /* an iteration found fewer than min_inliers inliers, or a system that
+                                   is not positive definite; the pose is that of the iteration before */
+
+/* Parameters of the point-to-plane ICP.  The defaults of the Python wrappers: 0.1 m, cos 30 deg,
+ * stride 1, 10 iterations, 100 inliers, 1e-5 rad, 1e-5 m. */
+typedef struct {
+    double dist_max;      /* m: a pair further apart is no inlier (> 0) */
+    double cos_min;       /* the least cosine between the frame's and the model's normal ([-1, 1]) */
+    int32_t stride;       /* only pixels with u % stride == 0 and v % stride == 0 are sampled (>= 1) */
+    int32_t max_iter;     /* 1 .. TSDF_ICP_MAX_ITER */
+    int64_t min_inliers;  /* fewer inliers: lost */
+    double eps_rot;       /* rad */
+    double eps_trans;     /* m */
+} tsdf_icp_params_t;
+
+typedef struct {
+    int32_t status;      /* TSDF_TRACK_* */
+    int32_t iterations;  /* linearisations run (a lost one included) */
+    int64_t inliers;     /* of the last linearisation */
+    int64_t candidates;  /* of the last linearisation: pixels with a vertex and a normal (codes 2..6) */
+    double rms;          /* sqrt(sum r^2 / inliers) of the last linearisation, metres */
+    double w_norm;       /* |w| and |t| of the last update (0 after a lost iteration) */
+    double t_norm;
+} tsdf_track_info_t;
+
 /* Cumulative counters since create/reset (or the last tsdf_*_stats call with reset != 0). */
 typedef struct {
     int64_t frames;           /* frames integrated */
@@ -218,6 +247,28 @@ int tsdf_mc_table(int8_t* tri, uint8_t* ntri);
 int tsdf_dense_raycast(tsdf_dense_t* h, int height, int width, const double K[9],
                        const double cam_pose[16], double z_near, double z_far, double z_step,
                        float* depth, float* normals, uint8_t* colors, int flags);
+/* Track a depth frame against the fused model (not in the reference): frame-to-model
+ * point-to-plane ICP, single resolution, geometry only.  The model maps are this handle's own
+ * raycast (depth and normals, height x width through K, with z_near / z_far / z_step as there) at
+ * pose_guess (camera-to-world); the frame (depth of depth_kind, height x width through the same K;
+ * TSDF_DEPTH_INVALID_65535 is honoured; a host pointer, or a device pointer with TSDF_DEVICE_PTRS)
+ * is aligned to them starting from the relative pose M_0 = I, for at most params->max_iter
+ * iterations of linearise (tsdf_icp_linearize's arithmetic), solve and M <- E(xi) M, all queued on
+ * the handle's stream and run without a host synchronisation in between; the call then synchronises
+ * once and copies the iterations' records back once (TSDF_ASYNC is accepted and changes nothing:
+ * the result is a host value).  out_pose = pose_guess * M in f64.  info (may be NULL) describes the
+ * end; trajectory (may be NULL) receives (max_iter + 1) x 16 doubles: M_0 = I, then M after each
+ * iteration run (a lost iteration repeats its predecessor), zeros beyond.  Deferred frames run
+ * first.  A lost track is no error: the call returns 0, info->status is TSDF_TRACK_LOST and
+ * out_pose is the last good pose (pose_guess when the first iteration was lost).  Two calls on the
+ * same state and inputs give byte-identical results (no floating-point atomics).  TSDF_E_ARG:
+ * stride < 1, max_iter outside [1, TSDF_ICP_MAX_ITER], dist_max <= 0, cos_min outside [-1, 1],
+ * a negative min_inliers / eps, a bad image size or depth_kind, a NULL depth / K / pose_guess /
+ * params / out_pose, and whatever the raycast refuses (its z arguments, a cyclic column shard). */
+int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width,
+                     const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                     double z_near, double z_far, double z_step, double out_pose[16],
+                     tsdf_track_info_t* info, double* trajectory, int flags);
 int tsdf_dense_stats(tsdf_dense_t* h, tsdf_stats_t* out, int reset);
 int tsdf_dense_set_profiling(tsdf_dense_t* h, int on);
 
@@ -290,6 +341,17 @@ int tsdf_hash_raycast(tsdf_hash_t* h, int height, int width, const double K[9],
  * returning on a handle with profiling on (tsdf_*_set_profiling): the live-bit pass (about 0 when
  * the bits were current) and the march.  -1 before any such call. */
 int tsdf_raycast_last_ms(double* live_ms, double* march_ms);
+/* tsdf_dense_track on the table (the model maps are tsdf_hash_raycast's).  TSDF_E_ARG also for a
+ * shard (n_shards > 1). */
+int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width,
+                    const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                    double z_near, double z_far, double z_step, double out_pose[16],
+                    tsdf_track_info_t* info, double* trajectory, int flags);
+/* HIP-event times, in milliseconds, of the calling thread's last track on a handle with profiling
+ * on: ms[0] the raycast, ms[1] the setup (frame copy, state, pixel tables), ms[2] and ms[3] the
+ * linearise and the finish launches summed over the iterations run, ms[4] the launches that
+ * fell through after a status was set.  -1 before any such call. */
+int tsdf_track_last_ms(double ms[5], int* iterations);
 int tsdf_hash_sync(tsdf_hash_t* h);
 /* sync, then a pool on mapped memory hands the memory above its live blocks back (pool_capacity
  * = live blocks + ~3 %, in whole 8 MB pieces; the live blocks move into fresh mapped ranges by one
@@ -315,6 +377,28 @@ int tsdf_hash_frames_per_launch(tsdf_hash_t* h, int* n);
 int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int height, int width,
                         const double K[9], const double* cam_poses, int flags, int device,
                         double* max_depth, double* frustum_pts, double bounds[6]);
+
+/* One linearisation of the point-to-plane ICP, without a handle, on HIP device
+ * `device`.  depth: the frame, Hf x Wf of depth_kind through Kf (TSDF_DEPTH_INVALID_65535 honoured);
+ * model_depth Hm x Wm f32 and model_normals Hm x Wm x 3 f32 (world axes): the maps of a raycast at
+ * model_pose through Km; rel_pose: M, frame camera to model camera.  Per sampled pixel (params->
+ * stride) a code -- 0 not sampled, last row / column or no depth; 1 no neighbour depth or no
+ * normal; 2 behind the model camera or outside its image; 3 no model surface there; 4 further than
+ * dist_max; 5 normals' cosine below cos_min; 6 inlier -- and for an inlier the residual r and the row
+ * J = (p x n, n), every operation a separately rounded f32 operation in the fixed order of §7e
+ * (restated by tests/icp_ref.py).  sums: the 21 upper-triangle entries of sum J_i J_j (row-major),
+ * the 6 of sum J_i r, and sum r r, over the inliers, in f64 (every term an exact product; the
+ * order of addition is fixed by the image size, the stride and the device: repeatable to the
+ * byte, no floating-point atomics).  counts: inliers, candidates (codes 2..6).  code (Hf x Wf u8)
+ * and residual (Hf x Wf f32, 0 where code != 6) may be NULL.  The image pointers (depth, the model
+ * maps, code, residual) are host pointers, or all device pointers with TSDF_DEVICE_PTRS; host
+ * images go through device buffers kept per device (grown on demand).  Synchronous.  Only
+ * dist_max, cos_min and stride of params matter (all of it is validated). */
+int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, int Wf, const double Kf[9],
+                       const double rel_pose[16], const float* model_depth, const float* model_normals,
+                       int Hm, int Wm, const double Km[9], const double model_pose[16],
+                       const tsdf_icp_params_t* params, double sums[28], int64_t counts[2],
+                       uint8_t* code, float* residual, int flags);
 
 /* hash_function over n coordinate triples (host in, host out), computed on the device.  The
  * same arithmetic as the kernels' home-slot computation. */

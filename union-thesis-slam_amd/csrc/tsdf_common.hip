@@ -786,6 +786,8 @@ void Base::release() {
     ray_live = nullptr;
     ray_live_words = 0;
     ray_live_gen = 0;
+    icp_ctx_free(icp);
+    icp = nullptr;
     for (int k = 0; k < 3; ++k) {
         if (ray_out[k]) (void)hipFree(ray_out[k]);
         ray_out[k] = nullptr;

@@ -66,6 +66,10 @@ struct Profiler {
 constexpr int kSets = 3;
 constexpr int kSlots = 4;
 
+// Device buffers of a handle's tracks (tsdf_track.hip), created by the first one.
+struct IcpCtx;
+void icp_ctx_free(IcpCtx* c);
+
 // State common to the dense and hash handles.
 struct Base {
     int device = 0;
@@ -246,6 +250,7 @@ struct Base {
     bool ray_skip = true;
     void* ray_out[3] = {};  // device buffers of host-pointer raycasts (depth, normals, colours), grown on demand
     size_t ray_out_bytes[3] = {};
+    IcpCtx* icp = nullptr;  // tracking buffers (model maps, frame copy, partial sums, iteration records), grown on demand
     int read_stats(tsdf_stats_t* out, int reset);
     // Vol::canon from the first n_vox voxels of the pool (after a set or an import; synchronous)
     int check_canon(long long n_vox);

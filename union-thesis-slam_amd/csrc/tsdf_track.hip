@@ -1,0 +1,728 @@
+// tsdf_track.hip -- camera tracking against the fused model: frame-to-model
+// point-to-plane ICP, single resolution, geometry only.  Not in the reference (its poses come from
+// files).  A depth frame is aligned against the depth and normal maps of a raycast (§7d): per
+// sampled pixel a projective association and one row of the linearised point-to-plane system, a
+// deterministic reduction to the 6x6 normal equations, and the Cholesky solve and pose update on
+// the device, so that an N-iteration alignment costs one host synchronisation.
+//
+// The contract (restated in NumPy by tests/icp_ref.py; codes and residuals matched bit for bit):
+// everything per pixel is a separately rounded f32 operation in the model camera's frame, the sums
+// are f64 sums of exact products of two f32 values.  See §7e for the steps; the codes are
+//   0 not sampled / last row or column / no depth     1 no neighbour depth or degenerate normal
+//   2 behind the model camera or outside its image     3 no model surface there
+//   4 too far (dist_max)    5 normals disagree (cos_min)    6 inlier
+//
+// Two kernels per iteration.  k_icp_linearize: one lane per sampled pixel over a grid-stride loop,
+// 28 f64 sums and 2 counts per lane, a butterfly over the wave, the waves of a workgroup through
+// LDS in wave order, one partial record per workgroup.  k_icp_finish (one workgroup of 1024): the partial
+// records in a fixed order, then one lane solves and updates.  No floating-point atomics anywhere:
+// the order of every addition is fixed by the launch shape, which depends on the image size, the
+// stride and the device only.  The finish is a kernel of its own, not the last workgroup of the
+// linearise: a kernel boundary makes the partial records visible across the XCDs' L2s by itself,
+// where a last-arriver protocol needs an agent-scope release per workgroup, a ticket atomic and an
+// acquire, for the price of one more launch of a few microseconds (§7e).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "tsdf_host.h"
+
+using namespace tsdf;
+
+namespace tsdf {
+
+constexpr int kIcpWG = 256;
+constexpr int kIcpRec = 32;       // doubles per partial record: 28 sums, inliers, candidates, 2 unused
+constexpr int kIcpMaxIter = TSDF_ICP_MAX_ITER;
+constexpr int kIcpRunning = 0;    // internal status while iterating (the public ones: TSDF_TRACK_*)
+
+// The iteration state, in device memory.
+struct IcpState {
+    double M[16];  // frame camera -> model camera
+    int status;
+    int iters;     // linearisations run
+};
+
+// One iteration's record (device array indexed by iteration; copied back once).
+struct IcpRecord {
+    double M[16];        // after the iteration (unchanged by a lost one)
+    double sums[28];     // 21 upper-triangle entries of sum J_i J_j (row-major), 6 of sum J_i r, sum r r
+    long long inliers, candidates;
+    double w_norm, t_norm;
+    int status;          // after the iteration
+    int pad;
+};
+
+// Device buffers of a handle's tracks, or of a device's handle-less linearisations: grown on
+// demand, never allocated per call once they fit.
+struct IcpCtx {
+    int device = 0;
+    hipStream_t stream = nullptr;  // the handle's, or the context's own
+    bool own_stream = false;
+    void* buf[8] = {};             // see the enum
+    size_t bytes[8] = {};
+    std::mutex mu;
+    void release();
+};
+enum { kBufDepth, kBufModelD, kBufModelN, kBufCode, kBufResid, kBufTables, kBufPartial, kBufState };
+
+void IcpCtx::release() {
+    for (int i = 0; i < 8; ++i) {
+        if (buf[i]) (void)hipFree(buf[i]);
+        buf[i] = nullptr;
+        bytes[i] = 0;
+    }
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+}
+
+void icp_ctx_free(IcpCtx* c) {
+    if (!c) return;
+    c->release();
+    delete c;
+}
+
+}  // namespace tsdf
+
+namespace {
+
+struct IcpArgs {
+    const void* depth;  // Hf x Wf, u16 mm or f64 m
+    int dk, inval;
+    int Hf, Wf, Hm, Wm;
+    int stride, su, sv;  // sampled pixels per row / rows
+    const float* dm;     // Hm x Wm
+    const float* nm;     // Hm x Wm x 3, world axes
+    const float *xf, *yf, *xm, *ym;  // pixel direction tables of the two cameras
+    float Rm[9];         // rotation of model_pose (row-major)
+    float fxm, fym, cxm, cym;
+    float dist_max, cos_min;
+    const IcpState* st;
+    double* partial;     // gridDim.x records of kIcpRec doubles
+    unsigned char* code;
+    float* resid;
+};
+
+// x_u = f32((u - cx) / fx), y_v = f32((v - cy) / fy): f64, one rounding (§7d step 1)
+__global__ void k_icp_tables(int Wf, int Hf, int Wm, int Hm, double fxf, double fyf, double cxf, double cyf, double fxm,
+                             double fym, double cxm, double cym, float* t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < Wf) t[i] = (float)(((double)i - cxf) / fxf);
+    else if (i < Wf + Hf) t[i] = (float)(((double)(i - Wf) - cyf) / fyf);
+    else if (i < Wf + Hf + Wm) t[i] = (float)(((double)(i - Wf - Hf) - cxm) / fxm);
+    else if (i < Wf + Hf + Wm + Hm) t[i] = (float)(((double)(i - Wf - Hf - Wm) - cym) / fym);
+}
+
+__global__ void k_icp_init(IcpState* st, const double* M) {
+    if (threadIdx.x < 16) st->M[threadIdx.x] = M ? M[threadIdx.x] : (threadIdx.x % 5 == 0 ? 1.0 : 0.0);
+    if (threadIdx.x == 0) {
+        st->status = kIcpRunning;
+        st->iters = 0;
+    }
+}
+
+template <int DK>
+__device__ inline float depth_at(const IcpArgs& a, int u, int v) {
+    const size_t p = (size_t)v * a.Wf + u;
+    if (DK == TSDF_DEPTH_U16_MM) {
+        const unsigned mm = ((const unsigned short*)a.depth)[p];
+        if (a.inval && mm == 65535u) return 0.0f;
+        return (float)((double)mm / 1000.0);
+    }
+    return (float)((const double*)a.depth)[p];
+}
+
+__device__ inline bool good_depth(float d) { return d > 0.0f && d < INFINITY; }
+
+template <int DK>
+__global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
+    if (a.st->status != kIcpRunning) return;  // a status is set: the queued launches fall through
+    float M[12];
+    for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
+    const float dist2 = a.dist_max * a.dist_max;
+
+    double s[28];
+#pragma unroll
+    for (int i = 0; i < 28; ++i) s[i] = 0.0;
+    unsigned n_in = 0, n_cand = 0;
+
+    const long long n = (long long)a.su * a.sv;
+    for (long long i = (long long)blockIdx.x * kIcpWG + threadIdx.x; i < n; i += (long long)gridDim.x * kIcpWG) {
+        const int u = (int)(i % a.su) * a.stride, v = (int)(i / a.su) * a.stride;
+        int code = 0;
+        float r = 0.0f, J[6];
+        do {
+            if (u >= a.Wf - 1 || v >= a.Hf - 1) break;
+            const float d = depth_at<DK>(a, u, v);
+            if (!good_depth(d)) break;
+            code = 1;
+            const float dr = depth_at<DK>(a, u + 1, v), dd = depth_at<DK>(a, u, v + 1);
+            if (!good_depth(dr) || !good_depth(dd)) break;
+            const float xu = a.xf[u], xr = a.xf[u + 1], yv = a.yf[v], yd = a.yf[v + 1];
+            const float V[3] = {xu * d, yv * d, d};
+            const float A[3] = {xr * dr - V[0], yv * dr - V[1], dr - V[2]};
+            const float B[3] = {xu * dd - V[0], yd * dd - V[1], dd - V[2]};
+            const float c[3] = {B[1] * A[2] - B[2] * A[1], B[2] * A[0] - B[0] * A[2], B[0] * A[1] - B[1] * A[0]};
+            const float l = __fsqrt_rn((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+            if (l == 0.0f) break;
+            const float nf[3] = {c[0] / l, c[1] / l, c[2] / l};
+            float p[3], m[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                p[k] = ((M[4 * k] * V[0] + M[4 * k + 1] * V[1]) + M[4 * k + 2] * V[2]) + M[4 * k + 3];
+                m[k] = (M[4 * k] * nf[0] + M[4 * k + 1] * nf[1]) + M[4 * k + 2] * nf[2];
+            }
+            code = 2;
+            if (p[2] <= 0.0f) break;
+            const float uf = rintf(a.fxm * (p[0] / p[2]) + a.cxm), vf = rintf(a.fym * (p[1] / p[2]) + a.cym);
+            if (!(uf >= 0.0f && uf <= (float)(a.Wm - 1) && vf >= 0.0f && vf <= (float)(a.Hm - 1))) break;
+            const int um = (int)uf, vm = (int)vf;
+            const size_t pm = (size_t)vm * a.Wm + um;
+            const float dm = a.dm[pm];
+            const float nw[3] = {a.nm[3 * pm], a.nm[3 * pm + 1], a.nm[3 * pm + 2]};
+            code = 3;
+            if (!(dm > 0.0f) || (nw[0] == 0.0f && nw[1] == 0.0f && nw[2] == 0.0f)) break;
+            const float q[3] = {a.xm[um] * dm, a.ym[vm] * dm, dm};
+            float nn[3], e[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                nn[k] = (a.Rm[k] * nw[0] + a.Rm[3 + k] * nw[1]) + a.Rm[6 + k] * nw[2];
+                e[k] = q[k] - p[k];
+            }
+            code = 4;
+            if ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2] > dist2) break;
+            code = 5;
+            if ((nn[0] * m[0] + nn[1] * m[1]) + nn[2] * m[2] < a.cos_min) break;
+            code = 6;
+            r = (nn[0] * e[0] + nn[1] * e[1]) + nn[2] * e[2];
+            J[0] = p[1] * nn[2] - p[2] * nn[1];
+            J[1] = p[2] * nn[0] - p[0] * nn[2];
+            J[2] = p[0] * nn[1] - p[1] * nn[0];
+            J[3] = nn[0];
+            J[4] = nn[1];
+            J[5] = nn[2];
+        } while (false);
+        if (code >= 2) ++n_cand;
+        if (code == 6) {
+            ++n_in;
+            int k = 0;
+#pragma unroll
+            for (int x = 0; x < 6; ++x)
+#pragma unroll
+                for (int y = x; y < 6; ++y) s[k++] += (double)J[x] * (double)J[y];
+#pragma unroll
+            for (int x = 0; x < 6; ++x) s[21 + x] += (double)J[x] * (double)r;
+            s[27] += (double)r * (double)r;
+        }
+        const size_t pf = (size_t)v * a.Wf + u;
+        if (a.code) a.code[pf] = (unsigned char)code;
+        if (a.resid) a.resid[pf] = r;
+    }
+
+    // the wave: a butterfly (every lane ends with the same sum, formed in the same order)
+#pragma unroll
+    for (int i = 0; i < 28; ++i)
+        for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+    for (int o = 32; o > 0; o >>= 1) {
+        n_in += __shfl_xor(n_in, o);
+        n_cand += __shfl_xor(n_cand, o);
+    }
+    // the workgroup: through LDS, waves added in wave order
+    __shared__ double sh[kIcpWG / 64][kIcpRec];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 28; ++i) sh[wave][i] = s[i];
+        sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
+        sh[wave][29] = (double)n_cand;
+    }
+    __syncthreads();
+    if (threadIdx.x < 30) {
+        double t = sh[0][threadIdx.x];
+        for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
+        a.partial[(size_t)blockIdx.x * kIcpRec + threadIdx.x] = t;
+    }
+}
+
+struct FinishArgs {
+    const double* partial;
+    int n_partial;
+    IcpState* st;
+    IcpRecord* rec;   // this iteration's
+    int solve;        // 0: sums only (tsdf_icp_linearize)
+    int last;         // the last iteration of the call: still running afterwards means max_iter
+    long long min_inliers;
+    double eps_rot, eps_trans;
+};
+
+constexpr int kFinSlices = 32;
+constexpr int kFinWG = kFinSlices * kIcpRec;  // 1024: the loads of the partial records spread over many lanes
+
+__global__ __launch_bounds__(kFinWG) void k_icp_finish(FinishArgs a) {
+    if (a.st->status != kIcpRunning) return;
+    // the partial records: column j by slice (records slice, slice + 32, ...), then the slices in order
+    __shared__ double sh[kFinSlices][kIcpRec];
+    __shared__ double tot[kIcpRec];
+    const int j = threadIdx.x & 31, slice = threadIdx.x >> 5;
+    double t = 0.0;
+    if (j < 30) {
+#pragma unroll 4
+        for (int g = slice; g < a.n_partial; g += kFinSlices) t += a.partial[(size_t)g * kIcpRec + j];
+    }
+    sh[slice][j] = t;
+    __syncthreads();
+    if (threadIdx.x < 30) {
+        double x = sh[0][threadIdx.x];
+        for (int k = 1; k < kFinSlices; ++k) x += sh[k][threadIdx.x];
+        tot[threadIdx.x] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+
+    IcpRecord& R = *a.rec;
+    for (int i = 0; i < 28; ++i) R.sums[i] = tot[i];
+    R.inliers = (long long)tot[28];
+    R.candidates = (long long)tot[29];
+    R.w_norm = R.t_norm = 0.0;
+    double M[16];
+    for (int i = 0; i < 16; ++i) M[i] = a.st->M[i];
+    int status = kIcpRunning;
+    if (a.solve) {
+        // A = L L^T (lower triangle, in place), then the two triangular solves
+        double L[6][6], b[6];
+        int k = 0;
+        for (int x = 0; x < 6; ++x)
+            for (int y = x; y < 6; ++y) L[y][x] = tot[k++];
+        for (int x = 0; x < 6; ++x) b[x] = tot[21 + x];
+        bool ok = R.inliers >= a.min_inliers;
+        for (int c = 0; c < 6 && ok; ++c) {
+            double d = L[c][c];
+            for (int e = 0; e < c; ++e) d -= L[c][e] * L[c][e];
+            if (!(d > 0.0) || !(d < INFINITY)) {
+                ok = false;
+                break;
+            }
+            d = sqrt(d);
+            L[c][c] = d;
+            for (int r = c + 1; r < 6; ++r) {
+                double x = L[r][c];
+                for (int e = 0; e < c; ++e) x -= L[r][e] * L[c][e];
+                L[r][c] = x / d;
+            }
+        }
+        if (!ok) {
+            status = TSDF_TRACK_LOST;
+        } else {
+            double y[6], xi[6];
+            for (int r = 0; r < 6; ++r) {
+                double x = b[r];
+                for (int e = 0; e < r; ++e) x -= L[r][e] * y[e];
+                y[r] = x / L[r][r];
+            }
+            for (int r = 5; r >= 0; --r) {
+                double x = y[r];
+                for (int e = r + 1; e < 6; ++e) x -= L[e][r] * xi[e];
+                xi[r] = x / L[r][r];
+            }
+            // E = Rodrigues(w) with translation t; M <- E M
+            const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+            const double th2 = (w0 * w0 + w1 * w1) + w2 * w2, th = sqrt(th2);
+            double A = 1.0, Bc = 0.5;
+            if (th > 1e-8) {
+                A = sin(th) / th;
+                Bc = (1.0 - cos(th)) / th2;
+            }
+            const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+            double E[9];
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) {
+                    const double k2 = (K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c]) + K[3 * r + 2] * K[6 + c];
+                    E[3 * r + c] = ((r == c ? 1.0 : 0.0) + A * K[3 * r + c]) + Bc * k2;
+                }
+            double N[16];
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    double x = (E[3 * r] * M[c] + E[3 * r + 1] * M[4 + c]) + E[3 * r + 2] * M[8 + c];
+                    if (c == 3) x += xi[3 + r];
+                    N[4 * r + c] = x;
+                }
+            N[12] = N[13] = N[14] = 0.0;
+            N[15] = 1.0;
+            bool finite = true;
+            for (int i = 0; i < 12; ++i) finite = finite && N[i] - N[i] == 0.0;
+            if (!finite) {
+                status = TSDF_TRACK_LOST;
+            } else {
+                for (int i = 0; i < 16; ++i) M[i] = N[i];
+                R.w_norm = th;
+                R.t_norm = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+                if (R.w_norm <= a.eps_rot && R.t_norm <= a.eps_trans) status = TSDF_TRACK_CONVERGED;
+                else if (a.last) status = TSDF_TRACK_MAX_ITER;
+            }
+        }
+    }
+    for (int i = 0; i < 16; ++i) {
+        R.M[i] = M[i];
+        a.st->M[i] = M[i];
+    }
+    R.status = status;
+    a.st->iters += 1;
+    a.st->status = status;
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+int ensure(IcpCtx& c, int which, size_t need) {
+    if (need <= c.bytes[which]) return TSDF_OK;
+    if (c.buf[which]) {
+        TSDF_HIP(hipStreamSynchronize(c.stream));
+        TSDF_HIP(hipFree(c.buf[which]));
+        c.buf[which] = nullptr;
+        c.bytes[which] = 0;
+    }
+    TSDF_HIP(hipMalloc(&c.buf[which], need));
+    c.bytes[which] = need;
+    return TSDF_OK;
+}
+
+bool bad_size(int H, int W) {
+    return H <= 0 || W <= 0 || H >= (1 << 24) || W >= (1 << 24) || (long long)H * W >= (1ll << 28);
+}
+
+int check_params(const tsdf_icp_params_t* p) {
+    if (!p) return set_error(TSDF_E_ARG, "null params pointer");
+    if (p->stride < 1) return set_error(TSDF_E_ARG, "stride must be >= 1 (got %d)", p->stride);
+    if (p->max_iter < 1 || p->max_iter > kIcpMaxIter)
+        return set_error(TSDF_E_ARG, "max_iter must be in [1, %d] (got %d)", kIcpMaxIter, p->max_iter);
+    if (!(p->dist_max > 0.0) || !((float)p->dist_max > 0.0f) || !std::isfinite((float)p->dist_max))
+        return set_error(TSDF_E_ARG, "dist_max must be > 0 (got %g)", p->dist_max);
+    if (!(p->cos_min >= -1.0 && p->cos_min <= 1.0))
+        return set_error(TSDF_E_ARG, "cos_min must be in [-1, 1] (got %g)", p->cos_min);
+    if (p->min_inliers < 0) return set_error(TSDF_E_ARG, "min_inliers must be >= 0 (got %lld)", (long long)p->min_inliers);
+    if (!(p->eps_rot >= 0.0) || !(p->eps_trans >= 0.0))
+        return set_error(TSDF_E_ARG, "eps_rot / eps_trans must be >= 0 (got %g, %g)", p->eps_rot, p->eps_trans);
+    return TSDF_OK;
+}
+
+struct Cameras {
+    int Hf, Wf, Hm, Wm;
+    const double *Kf, *Km, *model_pose;
+};
+
+unsigned linearize_grid(const IcpArgs& a, int n_cu) {
+    const long long n = (long long)a.su * a.sv;
+    return (unsigned)std::max(1ll, std::min<long long>((n + kIcpWG - 1) / kIcpWG, (long long)std::max(n_cu, 1) * 4));
+}
+
+// The arguments of the linearise launches of one call, with the tables queued on the stream.
+int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, int flags, const void* depth,
+            const float* dm, const float* nm, unsigned char* code, float* resid, int n_cu, IcpArgs* out, unsigned* grid) {
+    IcpArgs a{};
+    a.depth = depth;
+    a.dk = dk;
+    a.inval = (flags & TSDF_DEPTH_INVALID_65535) ? 1 : 0;
+    a.Hf = cam.Hf;
+    a.Wf = cam.Wf;
+    a.Hm = cam.Hm;
+    a.Wm = cam.Wm;
+    a.stride = p.stride;
+    a.su = (cam.Wf + p.stride - 1) / p.stride;
+    a.sv = (cam.Hf + p.stride - 1) / p.stride;
+    a.dm = dm;
+    a.nm = nm;
+    const size_t nt = (size_t)cam.Wf + cam.Hf + cam.Wm + cam.Hm;
+    TSDF_TRY(ensure(c, kBufTables, nt * sizeof(float)));
+    float* t = (float*)c.buf[kBufTables];
+    a.xf = t;
+    a.yf = t + cam.Wf;
+    a.xm = a.yf + cam.Hf;
+    a.ym = a.xm + cam.Wm;
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) a.Rm[3 * r + k] = (float)cam.model_pose[4 * r + k];
+    a.fxm = (float)cam.Km[0];
+    a.fym = (float)cam.Km[4];
+    a.cxm = (float)cam.Km[2];
+    a.cym = (float)cam.Km[5];
+    a.dist_max = (float)p.dist_max;
+    a.cos_min = (float)p.cos_min;
+    a.st = (const IcpState*)c.buf[kBufState];
+    *grid = linearize_grid(a, n_cu);
+    TSDF_TRY(ensure(c, kBufPartial, (size_t)*grid * kIcpRec * sizeof(double)));
+    a.partial = (double*)c.buf[kBufPartial];
+    a.code = code;
+    a.resid = resid;
+    hipLaunchKernelGGL(k_icp_tables, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c.stream, cam.Wf, cam.Hf, cam.Wm,
+                       cam.Hm, cam.Kf[0], cam.Kf[4], cam.Kf[2], cam.Kf[5], cam.Km[0], cam.Km[4], cam.Km[2], cam.Km[5], t);
+    TSDF_HIP(hipGetLastError());
+    // pixels no lane visits (stride > 1) read code 0, residual 0
+    if (p.stride > 1) {
+        if (code) TSDF_HIP(hipMemsetAsync(code, 0, (size_t)cam.Hf * cam.Wf, c.stream));
+        if (resid) TSDF_HIP(hipMemsetAsync(resid, 0, (size_t)cam.Hf * cam.Wf * sizeof(float), c.stream));
+    }
+    *out = a;
+    return TSDF_OK;
+}
+
+int launch_iteration(IcpCtx& c, const IcpArgs& a, unsigned grid, IcpRecord* rec, int solve, int last,
+                     const tsdf_icp_params_t& p, hipEvent_t ev_mid = nullptr, hipEvent_t ev_end = nullptr) {
+    if (a.dk == TSDF_DEPTH_U16_MM) hipLaunchKernelGGL(k_icp_linearize<TSDF_DEPTH_U16_MM>, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
+    else hipLaunchKernelGGL(k_icp_linearize<TSDF_DEPTH_F64_M>, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
+    TSDF_HIP(hipGetLastError());
+    if (ev_mid) TSDF_HIP(hipEventRecord(ev_mid, c.stream));
+    FinishArgs f{};
+    f.partial = a.partial;
+    f.n_partial = (int)grid;
+    f.st = (IcpState*)c.buf[kBufState];
+    f.rec = rec;
+    f.solve = solve;
+    f.last = last;
+    f.min_inliers = p.min_inliers;
+    f.eps_rot = p.eps_rot;
+    f.eps_trans = p.eps_trans;
+    hipLaunchKernelGGL(k_icp_finish, dim3(1), dim3(kFinWG), 0, c.stream, f);
+    TSDF_HIP(hipGetLastError());
+    if (ev_end) TSDF_HIP(hipEventRecord(ev_end, c.stream));
+    return TSDF_OK;
+}
+
+// state block: IcpState, 16 doubles of an uploaded pose, then the records
+constexpr size_t kStateOff = 0, kPoseOff = 256, kRecOff = 512;
+size_t state_bytes(int n_rec) { return kRecOff + sizeof(IcpRecord) * (size_t)n_rec; }
+
+// per-device contexts of the handle-less call
+constexpr int kMaxDev = 64;
+IcpCtx* g_dev_ctx[kMaxDev] = {};
+std::mutex g_dev_mu;
+
+// HIP-event times of the calling thread's last track on a handle with profiling on
+thread_local double g_track_ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, 0.0};
+
+int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const double*, double, double, double, float*,
+                                          float*, uint8_t*, int),
+          void* handle, const void* depth, int dk, int H, int W, const double* K, const double* pose_guess,
+          const tsdf_icp_params_t* p, double zn, double zf, double zs, double* out_pose, tsdf_track_info_t* info,
+          double* trajectory, int flags) {
+    Base& B = *S.b;
+    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
+    if (!K || !pose_guess) return set_error(TSDF_E_ARG, "null camera pointer");
+    if (!out_pose) return set_error(TSDF_E_ARG, "null out_pose pointer");
+    if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
+    if (bad_size(H, W)) return set_error(TSDF_E_ARG, "bad image size %dx%d", H, W);
+    TSDF_TRY(check_params(p));
+    if (!B.icp) {
+        B.icp = new IcpCtx();
+        B.icp->device = B.device;
+        B.icp->stream = B.stream;
+    }
+    IcpCtx& c = *B.icp;
+    const size_t px = (size_t)H * W;
+    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
+    TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
+    TSDF_TRY(ensure(c, kBufState, state_bytes(p->max_iter)));
+    const void* dd = depth;
+    if (!dev) {
+        const size_t nb = frame_bytes_depth(dk, H, W);
+        TSDF_TRY(ensure(c, kBufDepth, nb));
+        dd = c.buf[kBufDepth];
+    }
+    // profiling on: events around the raycast, the setup and every launch of the iterations
+    const bool timed = B.prof.on;
+    std::vector<hipEvent_t> ev(timed ? 3 + 2 * (size_t)p->max_iter : 0, nullptr);
+    struct EvGuard {
+        std::vector<hipEvent_t>& e;
+        ~EvGuard() {
+            for (auto x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev_guard{ev};
+    for (auto& e : ev) TSDF_HIP(hipEventCreate(&e));
+    if (timed) TSDF_HIP(hipEventRecord(ev[0], c.stream));
+    // the model maps: the handle's own raycast at pose_guess (it runs the deferred frames first and
+    // refuses what a raycast refuses)
+    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN], nullptr,
+                  TSDF_DEVICE_PTRS | TSDF_ASYNC));
+    if (timed) TSDF_HIP(hipEventRecord(ev[1], c.stream));
+    if (!dev) TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
+    char* sb = (char*)c.buf[kBufState];
+    IcpRecord* rec = (IcpRecord*)(sb + kRecOff);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)nullptr);
+    TSDF_HIP(hipGetLastError());
+    Cameras cam{H, W, H, W, K, K, pose_guess};
+    IcpArgs a;
+    unsigned grid;
+    TSDF_TRY(prepare(c, cam, *p, dk, flags, dd, (const float*)c.buf[kBufModelD], (const float*)c.buf[kBufModelN], nullptr,
+                     nullptr, B.n_cu, &a, &grid));
+    if (timed) TSDF_HIP(hipEventRecord(ev[2], c.stream));
+    for (int it = 0; it < p->max_iter; ++it)
+        TSDF_TRY(launch_iteration(c, a, grid, rec + it, 1, it == p->max_iter - 1, *p,
+                                  timed ? ev[3 + 2 * it] : nullptr, timed ? ev[4 + 2 * it] : nullptr));
+    // one synchronisation, one copy back
+    std::vector<char> host(state_bytes(p->max_iter));
+    TSDF_HIP(hipMemcpyAsync(host.data(), sb, host.size(), hipMemcpyDeviceToHost, c.stream));
+    TSDF_HIP(hipStreamSynchronize(c.stream));
+    const IcpState* st = (const IcpState*)(host.data() + kStateOff);
+    const IcpRecord* hr = (const IcpRecord*)(host.data() + kRecOff);
+    const int iters = std::min(std::max(st->iters, 0), p->max_iter);
+    if (timed) {
+        double ms[5] = {0, 0, 0, 0, 0};  // raycast, setup, linearise, finish (iterations run), fall-through launches
+        for (size_t i = 0; i + 1 < ev.size(); ++i) {
+            float x = 0.0f;
+            TSDF_HIP(hipEventElapsedTime(&x, ev[i], ev[i + 1]));
+            const int it = i < 2 ? 0 : (int)(i - 2) / 2;
+            ms[i < 2 ? i : (it >= iters ? 4 : 2 + (int)(i - 2) % 2)] += x;
+        }
+        for (int i = 0; i < 5; ++i) g_track_ms[i] = ms[i];
+        g_track_ms[5] = (double)iters;
+    }
+    // out_pose = pose_guess * M, f64, three-term sums left to right
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) {
+            double x = 0.0;
+            for (int e = 0; e < 4; ++e) x += pose_guess[4 * r + e] * st->M[4 * e + k];
+            out_pose[4 * r + k] = x;
+        }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->status = st->status;
+        info->iterations = iters;
+        if (iters > 0) {
+            const IcpRecord& L = hr[iters - 1];
+            info->inliers = L.inliers;
+            info->candidates = L.candidates;
+            info->rms = L.inliers > 0 ? std::sqrt(L.sums[27] / (double)L.inliers) : 0.0;
+            info->w_norm = L.w_norm;
+            info->t_norm = L.t_norm;
+        }
+    }
+    if (trajectory) {
+        memset(trajectory, 0, sizeof(double) * 16 * ((size_t)p->max_iter + 1));
+        for (int i = 0; i < 4; ++i) trajectory[5 * i] = 1.0;
+        for (int i = 0; i < iters; ++i) memcpy(trajectory + 16 * (i + 1), hr[i].M, sizeof(double) * 16);
+    }
+    return TSDF_OK;
+}
+
+int cast_dense(void* h, int H, int W, const double* K, const double* pose, double zn, double zf, double zs, float* d,
+               float* n, uint8_t* c, int flags) {
+    return tsdf_dense_raycast((tsdf_dense_t*)h, H, W, K, pose, zn, zf, zs, d, n, c, flags);
+}
+int cast_hash(void* h, int H, int W, const double* K, const double* pose, double zn, double zf, double zs, float* d,
+              float* n, uint8_t* c, int flags) {
+    return tsdf_hash_raycast((tsdf_hash_t*)h, H, W, K, pose, zn, zf, zs, d, n, c, flags);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, int Wf, const double Kf[9],
+                       const double rel_pose[16], const float* model_depth, const float* model_normals, int Hm, int Wm,
+                       const double Km[9], const double model_pose[16], const tsdf_icp_params_t* params, double sums[28],
+                       int64_t counts[2], uint8_t* code, float* residual, int flags) {
+    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
+    if (!model_depth || !model_normals) return set_error(TSDF_E_ARG, "null model map pointer");
+    if (!Kf || !Km || !rel_pose || !model_pose) return set_error(TSDF_E_ARG, "null camera pointer");
+    if (!sums || !counts) return set_error(TSDF_E_ARG, "null sums / counts pointer");
+    if (depth_kind != TSDF_DEPTH_U16_MM && depth_kind != TSDF_DEPTH_F64_M)
+        return set_error(TSDF_E_ARG, "bad depth_kind %d", depth_kind);
+    if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
+    if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
+    TSDF_TRY(check_params(params));
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(TSDF_E_NODEV, "no HIP device visible");
+    if (device < 0 || device >= ndev || device >= kMaxDev)
+        return set_error(TSDF_E_ARG, "device %d out of range [0,%d)", device, std::min(ndev, kMaxDev));
+    TSDF_HIP(hipSetDevice(device));
+    IcpCtx* cp;
+    {
+        std::lock_guard<std::mutex> lk(g_dev_mu);
+        if (!g_dev_ctx[device]) {
+            IcpCtx* n = new IcpCtx();
+            n->device = device;
+            n->own_stream = true;
+            const hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
+            if (e != hipSuccess) {
+                delete n;
+                TSDF_HIP(e);
+            }
+            g_dev_ctx[device] = n;
+        }
+        cp = g_dev_ctx[device];
+    }
+    IcpCtx& c = *cp;
+    std::lock_guard<std::mutex> lk(c.mu);  // one call at a time per device context
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
+    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    const size_t pf = (size_t)Hf * Wf, pm = (size_t)Hm * Wm;
+    TSDF_TRY(ensure(c, kBufState, state_bytes(1)));
+    const void* dd = depth;
+    const float *dm = model_depth, *nm = model_normals;
+    unsigned char* dcode = code;
+    float* dres = residual;
+    if (!dev) {
+        TSDF_TRY(ensure(c, kBufDepth, frame_bytes_depth(depth_kind, Hf, Wf)));
+        TSDF_TRY(ensure(c, kBufModelD, pm * sizeof(float)));
+        TSDF_TRY(ensure(c, kBufModelN, pm * 3 * sizeof(float)));
+        if (code) TSDF_TRY(ensure(c, kBufCode, pf));
+        if (residual) TSDF_TRY(ensure(c, kBufResid, pf * sizeof(float)));
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(depth_kind, Hf, Wf), hipMemcpyHostToDevice, c.stream));
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufModelD], model_depth, pm * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufModelN], model_normals, pm * 3 * sizeof(float), hipMemcpyHostToDevice, c.stream));
+        dd = c.buf[kBufDepth];
+        dm = (const float*)c.buf[kBufModelD];
+        nm = (const float*)c.buf[kBufModelN];
+        dcode = code ? (unsigned char*)c.buf[kBufCode] : nullptr;
+        dres = residual ? (float*)c.buf[kBufResid] : nullptr;
+    }
+    char* sb = (char*)c.buf[kBufState];
+    TSDF_HIP(hipMemcpyAsync(sb + kPoseOff, rel_pose, sizeof(double) * 16, hipMemcpyHostToDevice, c.stream));
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)(sb + kPoseOff));
+    TSDF_HIP(hipGetLastError());
+    Cameras cam{Hf, Wf, Hm, Wm, Kf, Km, model_pose};
+    IcpArgs a;
+    unsigned grid;
+    TSDF_TRY(prepare(c, cam, *params, depth_kind, flags, dd, dm, nm, dcode, dres, n_cu, &a, &grid));
+    TSDF_TRY(launch_iteration(c, a, grid, (IcpRecord*)(sb + kRecOff), 0, 1, *params));
+    IcpRecord rec;
+    TSDF_HIP(hipMemcpyAsync(&rec, sb + kRecOff, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
+    if (!dev) {
+        if (code) TSDF_HIP(hipMemcpyAsync(code, dcode, pf, hipMemcpyDeviceToHost, c.stream));
+        if (residual) TSDF_HIP(hipMemcpyAsync(residual, dres, pf * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+    }
+    TSDF_HIP(hipStreamSynchronize(c.stream));
+    memcpy(sums, rec.sums, sizeof(double) * 28);
+    counts[0] = rec.inliers;
+    counts[1] = rec.candidates;
+    return TSDF_OK;
+}
+
+int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                     const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
+                     double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return track(S, cast_dense, h, depth, depth_kind, height, width, K, pose_guess, params, z_near, z_far, z_step, out_pose,
+                 info, trajectory, flags);
+}
+
+int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                    const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
+                    double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return track(S, cast_hash, h, depth, depth_kind, height, width, K, pose_guess, params, z_near, z_far, z_step, out_pose,
+                 info, trajectory, flags);
+}
+
+int tsdf_track_last_ms(double ms[5], int* iterations) {
+    if (!ms || !iterations) return set_error(TSDF_E_ARG, "null pointer");
+    for (int i = 0; i < 5; ++i) ms[i] = g_track_ms[i];
+    *iterations = (int)g_track_ms[5];
+    return TSDF_OK;
+}
+
+}  // extern "C"

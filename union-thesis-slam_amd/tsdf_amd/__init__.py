@@ -11,4 +11,4 @@ Both run on hand-written gfx950 HIP kernels through the C-ABI in include/tsdf_hi
 """
 from . import _ffi  # noqa: F401
 
-__all__ = ["grid_fusion", "hash_fusion", "data_structures", "scene"]
+__all__ = ["grid_fusion", "hash_fusion", "data_structures", "scene", "tracking"]

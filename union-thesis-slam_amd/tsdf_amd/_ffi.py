@@ -60,6 +60,26 @@ class HashInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class IcpParams(ctypes.Structure):
+    """tsdf_icp_params_t"""
+    _fields_ = [("dist_max", ctypes.c_double), ("cos_min", ctypes.c_double), ("stride", ctypes.c_int32),
+                ("max_iter", ctypes.c_int32), ("min_inliers", ctypes.c_int64), ("eps_rot", ctypes.c_double),
+                ("eps_trans", ctypes.c_double)]
+
+
+class TrackInfo(ctypes.Structure):
+    """tsdf_track_info_t"""
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("inliers", ctypes.c_int64),
+                ("candidates", ctypes.c_int64), ("rms", ctypes.c_double), ("w_norm", ctypes.c_double),
+                ("t_norm", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+ICP_MAX_ITER = 64
+TRACK_STATUS = {1: "converged", 2: "max_iter", 3: "lost"}
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _I64 = ctypes.c_int64
@@ -111,6 +131,10 @@ SIGNATURES = {
     "tsdf_dense_raycast": [_P, _I, _I, _P, _P, _D, _D, _D, _P, _P, _P, _I],
     "tsdf_hash_raycast": [_P, _I, _I, _P, _P, _D, _D, _D, _P, _P, _P, _I],
     "tsdf_raycast_last_ms": [_P, _P],
+    "tsdf_icp_linearize": [_I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_dense_track": [_P, _P, _I, _I, _I, _P, _P, _P, _D, _D, _D, _P, _P, _P, _I],
+    "tsdf_hash_track": [_P, _P, _I, _I, _I, _P, _P, _P, _D, _D, _D, _P, _P, _P, _I],
+    "tsdf_track_last_ms": [_P, _P],
 }
 
 _lib = None

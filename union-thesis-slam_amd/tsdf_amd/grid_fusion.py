@@ -77,6 +77,14 @@ def frame_stack(depth, depth_kind, color, color_kind, device_ptrs):
     return depth, dk, color, ck
 
 
+def default_z_far(vol_bnds, cam_pose, z_near):
+    """The raycast's default z_far: the largest camera z of the volume's 8 corners."""
+    b = np.asarray(vol_bnds, dtype=np.float64)
+    corners = np.array([[b[0, i], b[1, j], b[2, k], 1.0] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
+    pose = np.asarray(cam_pose, dtype=np.float64).reshape(4, 4)
+    return float(max((np.linalg.inv(pose) @ corners.T)[2].max(), float(z_near)))
+
+
 def raycast_call(fn, handle, device, vol_bnds, voxel_size, cam_intr, cam_pose, hw, z_near, z_far, z_step,
                  normals, colors, out):
     """The raycast entry points' host side (tsdf_dense_raycast / tsdf_hash_raycast): defaults,
@@ -85,10 +93,8 @@ def raycast_call(fn, handle, device, vol_bnds, voxel_size, cam_intr, cam_pose, h
     pose = _ffi.f64(cam_pose, 16)
     if z_step is None:
         z_step = float(voxel_size)
-    if z_far is None:  # the largest camera z of the volume's 8 corners
-        b = np.asarray(vol_bnds, dtype=np.float64)
-        corners = np.array([[b[0, i], b[1, j], b[2, k], 1.0] for i in (0, 1) for j in (0, 1) for k in (0, 1)])
-        z_far = float(max((np.linalg.inv(pose.reshape(4, 4)) @ corners.T)[2].max(), float(z_near)))
+    if z_far is None:
+        z_far = default_z_far(vol_bnds, pose, z_near)
     K = _ffi.f64(cam_intr, 9)
     if out is not None:  # (out decides the fields: a None entry is not computed; normals / colors are not consulted)
         import torch
@@ -320,6 +326,24 @@ class TSDFVolume:
         `colors` are not consulted then.  Anything else in out raises ValueError."""
         return raycast_call("tsdf_dense_raycast", self._h, self.device, self._vol_bnds, self._voxel_size, cam_intr,
                             cam_pose, hw, z_near, z_far, z_step, normals, colors, out)
+
+    def track(self, depth_im, cam_intr, pose_guess, *, dist_max=0.1, angle_max_deg=30.0, stride=1, max_iter=10,
+              min_inliers=100, eps_rot=1e-5, eps_trans=1e-5, z_near=0.0, z_far=None, z_step=None,
+              return_info=False, invalid_65535=False):
+        """The camera pose of a depth frame, tracked against the fused model (tsdf_dense_track,
+        DESIGN.md §7e): point-to-plane ICP of depth_im (H,W; uint16 millimetres or metres, as
+        integrate() takes it) against this volume's raycast at pose_guess (camera-to-world), both
+        through cam_intr.  Returns the pose (4,4) f64; with return_info also a dict: status
+        ("converged", "max_iter" or "lost": then the pose is the last good one), iterations,
+        inliers, candidates, rms, w_norm, t_norm and trajectory, the relative poses M_0 = I, M_1, ...
+        (pose = pose_guess @ M_last).  A pair is an inlier within dist_max metres and
+        angle_max_deg between the normals; every stride-th pixel of every stride-th row is used;
+        z_near / z_far / z_step are the raycast's.  The tracking loop:
+            pose = vol.track(depth, K, last_pose); vol.integrate(rgb, depth, K, pose)"""
+        from . import tracking
+        return tracking.track_call("tsdf_dense_track", self._h, self._vol_bnds, self._voxel_size, depth_im, cam_intr,
+                                   pose_guess, dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot,
+                                   eps_trans, z_near, z_far, z_step, return_info, invalid_65535)
 
     def get_point_cloud(self):
         """grid_fusion.py:322-338: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""
