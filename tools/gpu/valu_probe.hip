@@ -86,6 +86,11 @@ KERNEL(k_cvt_u32_f32, float, BODY8_1("v_cvt_u32_f32"))
 KERNEL(k_cvt_ubyte1, float, BODY8_1("v_cvt_f32_ubyte1"))
 KERNEL(k_mad_u24, float, BODY8_3("v_mad_u32_u24"))
 KERNEL(k_pk_mul_f32, double, BODY8("v_pk_mul_f32", double, "v"))
+// the fixed-point pixel's integer tail (project_part)
+KERNEL(k_perm_b32, float, BODY8_3("v_perm_b32"))
+KERNEL(k_pk_min_u16, float, BODY8("v_pk_min_u16", float, "v"))
+KERNEL(k_dot2_u32_u16, float, BODY8_3("v_dot2_u32_u16"))
+KERNEL(k_min_u32, float, BODY8("v_min_u32", float, "v"))
 
 typedef void (*kd)(double*, long long*, double);
 typedef void (*kf)(float*, long long*, float);
@@ -156,6 +161,10 @@ int main() {
         run<float>("v_cvt_u32_f32", (kf)k_cvt_u32_f32, w);
         run<float>("v_cvt_f32_ubyte1", (kf)k_cvt_ubyte1, w);
         run<float>("v_mad_u32_u24", (kf)k_mad_u24, w);
+        run<float>("v_perm_b32", (kf)k_perm_b32, w);
+        run<float>("v_pk_min_u16", (kf)k_pk_min_u16, w);
+        run<float>("v_dot2_u32_u16", (kf)k_dot2_u32_u16, w);
+        run<float>("v_min_u32", (kf)k_min_u32, w);
     }
     return 0;
 }

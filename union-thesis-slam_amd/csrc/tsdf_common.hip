@@ -518,24 +518,24 @@ int Base::prepare_batch(Batch* bt, const void* depth, int dk, const void* color,
         fr->fy = (double)(float)K[4];
         fr->cx = (double)(float)K[2];
         fr->cy = (double)(float)K[5];
-        const double margin = frame_margin(W, H, fr->cx, fr->cy);
-        fr->half_m = 0.5 - margin;
         for (int j = 0; j < 4; ++j) {
             fr->Tf[j] = T[j] * fr->fx;
             fr->Tf[4 + j] = T[4 + j] * fr->fy;
         }
-        {  // the fast path's depth limit (fold_bound) as the high dword of a positive f64, rounded up
+        {  // the fast path's fixed-point constants and depth limit (tsdf_pixel.h)
             double wmax[3];
             for (int a = 0; a < 3; ++a) {
                 const long long gmax = (a == 0 ? (long long)vol.off[0] + col_gx(vol, vol.nb[0] - 1) + kBrickEdge
                                                : (long long)vol.off[a] + vol.dims[a]);
                 wmax[a] = fabs((double)vol.origin[a]) + vol.vs * (double)gmax + 1.0;
             }
-            const double zmin = fold_bound(T, fr->fx, fr->fy, wmax, margin);
-            long long bits;
-            std::memcpy(&bits, &zmin, sizeof bits);
-            const long long hi = (std::isfinite(zmin) && zmin < 1e300) ? (bits >> 32) + 1 : 0x7FEFFFFFll;
-            fr->zmin_hi = (int)std::min<long long>(hi, 0x7FEFFFFFll);
+            const PixelFixed pf = pixel_fixed(T, fr->fx, fr->fy, fr->cx, fr->cy, W, H, wmax);
+            fr->Cx = pf.Cx;
+            fr->Cy = pf.Cy;
+            fr->mm = pf.mm;
+            fr->whm1 = pf.whm1;
+            fr->wmul = pf.wmul;
+            fr->zmin_hi = pf.zmin_hi;
         }
         fr->ow = ow ? ow[first + i] : ow_default;
         fr->ow32 = (float)fr->ow;

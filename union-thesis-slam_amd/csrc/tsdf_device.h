@@ -16,6 +16,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "tsdf_pixel.h"
+
 namespace tsdf {
 
 constexpr int kBrickEdge = 8;
@@ -61,9 +63,10 @@ struct Frame {
     double T[12];             // rows 0..2 of inv(cam_pose), row-major
     double fx, fy, cx, cy;    // f64(f32(K))  (cam2pix casts intr to float32, grid_fusion.py:190)
     double ow;                // obs_weight as a Python float (f64)
-    double half_m;            // 0.5 - the fast pixel path's boundary margin (frame_margin)
     double Tf[8];             // the fast pixel path's rows: RN(T[0..3] * fx), RN(T[4..7] * fy)
-    int zmin_hi;              // ... and its depth limit: high dword of zmin (fold_bound, host)
+    double Cx, Cy;            // ... its 16.16 fixed-point addends: c + 0.5 + m*2^-16 + 1.5*2^36
+    unsigned mm, whm1, wmul;  // ... packed (2my, 2mx), (H - 1, W - 1), (W, 1)  (pixel_fixed, tsdf_pixel.h)
+    int zmin_hi;              // ... and its depth limit: high dword of zmin (INT_MAX: no fast path)
     float ow32;               // the same weight as NumPy's weak-scalar f32 (colour blend)
     int H, W;
     const void* depth;        // depth read by cull/integrate: u16 millimetres or f64 metres
@@ -232,7 +235,7 @@ __device__ inline int lane_id() { return threadIdx.x & 63; }
 __device__ unsigned long long fcmp64_mask(double a, double b, int pred) __asm("llvm.amdgcn.fcmp.i64.f64");
 __device__ unsigned long long fcmp32_mask(float a, float b, int pred) __asm("llvm.amdgcn.fcmp.i64.f32");
 __device__ unsigned long long icmp32_mask(unsigned a, unsigned b, int pred) __asm("llvm.amdgcn.icmp.i64.i32");
-constexpr int kCmpOGT = 2, kCmpOGE = 3, kCmpOLT = 4, kCmpUNE = 14, kCmpNE = 33, kCmpULT = 36, kCmpSGT = 38;
+constexpr int kCmpOGT = 2, kCmpOGE = 3, kCmpOLT = 4, kCmpUNE = 14, kCmpEQ = 32, kCmpNE = 33, kCmpULT = 36, kCmpSGT = 38;
 __device__ inline bool lane_in(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 // x = lane in m ? y : x, written in place (the register allocator otherwise gives the new value a
 // register of its own and copies it back where the paths merge)
@@ -495,7 +498,9 @@ __device__ inline unsigned depth_raw(const FrameBufs& fb, unsigned p) {
 template <int DK>
 __device__ inline double depth_m(const FrameBufs& fb, unsigned p, unsigned raw) {
     if (DK != 1) {  // two-term 1/1000 = C_HI + C_LO: exact for every u16 (tools/check_depth_conversion.c)
-        const double m = (double)raw;
+        // (texels: the dword as a signed integer -- the same value for a u16, and the prep's
+        // TSDF_TEXEL_INVALID for an invalid depth becomes a large negative depth)
+        const double m = DK == 2 ? (double)(int)raw : (double)raw;
         return fma(m, 0.001, m * -2.0858186326137145e-20);
     }
     return buf_ld_f64(fb.depth, (int)p, 0, 0, 0);
@@ -505,8 +510,12 @@ __device__ inline double depth_m(const FrameBufs& fb, unsigned p, unsigned raw) 
 // Reciprocal of z for the fast pixel path: the bare v_rcp_f64, accurate to 2^-24.4 relative
 // (random z in [1e-3, 1e3] and a 2^28-point mantissa sweep: tools/gpu/rcp_probe.hip), so
 // u = (x*fx)*rz + cx lies within |u - cx| * 2^-24.3 of the reference's (x*fx)/z + cx (< 3e-5 px
-// for 640x480).  Steps whose u is within frame_margin of a rounding boundary (or not finite) are recomputed with the reference's own division (a Newton-refined reciprocal
-// with a 1e-9 px margin ran 2.6 % slower: the two FMAs cost more than the extra slow steps).
+// for 640x480).  Steps whose u is within frame_margin of a rounding boundary are recomputed with the
+// reference's own division (a Newton-refined reciprocal with a 1e-9 px margin ran 2.6 % slower: the
+// two FMAs cost more than the extra slow steps).  The error budget of a step the fast path keeps:
+// |u - c| * 2^-24.3 (reciprocal) + E/z <= margin/4 (folded rows, fold_bound) against the margin
+// itself, which the fixed-point test grants in full: a kept coordinate is m*2^-16 - 2^-17 (the
+// FMA's rounding onto the 2^-16 grid) - |C's rounding error| >= margin from a boundary (tsdf_pixel.h).
 // ---------------------------------------------------------------------------------------------
 // RN(a / b) given y = RN(1 / b): Markstein's correction step.  q0 = RN(a*y) is within 1 ulp
 // of a/b, r = a - b*q0 is exact with an FMA, and RN(q0 + r*y) is then the correctly rounded
@@ -536,29 +545,8 @@ __device__ inline f2 div_rn32x2(f2 a, f2 b, f2 y) {  // div_rn32 on both lanes
     return pk_fma(r, y, q0);
 }
 
-// The fast path's pixel error is < |u - c| * 2^-24.3 (the bare reciprocal), and wherever the
-// boundary test matters |u - c| <= max(W, H) + max(|cx|, |cy|) -- a step closer than this margin to
-// a rounding boundary takes the exact path.  1e-4 px covers images up to ~1000 px; larger ones
-// scale it.  Host-side: stored per frame as half_m = 0.5 - margin.
-inline double frame_margin(int W, int H, double cx, double cy) {
-    const double span = (double)(W > H ? W : H) + fmax(fabs(cx), fabs(cy));
-    return fmax(1e-4, 1e-7 * span);
-}
-
-// The fast path folds fx, fy and the translation into its rows: X = fma(Tf2, pz, fma(Tf1, py,
-// fma(Tf0, px, Tf3))) with Tf = RN(T * f) -- four roundings, each within 2^-53 of its operands'
-// magnitudes, so |X - f * x| <= E = 8 * 2^-53 * f * (|T0| X + |T1| Y + |T2| Z + |T3|) for world
-// coordinates bounded by (X, Y, Z) (a factor 2 of slack).  Its pixel error E / z stays below a
-// quarter of the margin where z > zmin = 4 E / margin.  Returns zmin (host).
-inline double fold_bound(const double* T, double fx, double fy, const double wmax[3], double margin) {
-    double e = 0.0;
-    for (int r = 0; r < 2; ++r) {
-        const double* t = T + 4 * r;
-        const double s = fabs(t[0]) * wmax[0] + fabs(t[1]) * wmax[1] + fabs(t[2]) * wmax[2] + fabs(t[3]);
-        e = fmax(e, 8.0 * 0x1p-53 * (r == 0 ? fx : fy) * s);
-    }
-    return 4.0 * e / margin;
-}
+// The fast path's host side -- frame_margin, fold_bound and the 16.16 fixed-point constants of a
+// frame (pixel_fixed) -- is tsdf_pixel.h, in plain C for the CPU checker.
 
 // v_cvt_i32_f64 clamps out-of-range inputs to INT_MIN / INT_MAX (a C cast would be undefined
 // there, so the instruction is named directly)
@@ -566,6 +554,15 @@ __device__ inline int cvt_i32_sat(double x) {
     int r;
     asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(x));
     return r;
+}
+
+// The packed 16-bit ALU on the fixed-point pixel (one instruction each, as the ISA shows)
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ inline unsigned pk_min_u16(unsigned a, unsigned b) {  // v_pk_min_u16
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+__device__ inline unsigned dot2_u16(unsigned a, unsigned b) {  // v_dot2_u32_u16: a.lo * b.lo + a.hi * b.hi
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b), 0u, false);
 }
 
 __device__ inline double readlane_f64(double x, int l) {
@@ -621,12 +618,12 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
     // phase 1: project (grid_fusion.py:262-277).  Straight-line code over the z-steps (no
     // per-step branches) so the compiler can interleave their f64 chains; the rare steps whose
     // pixel lies within frame_margin of a rounding boundary are redone exactly afterwards.
-    // the pixel indices leave the f64 domain at once (saturating v_cvt_i32_f64: out-of-range
-    // values clamp to INT_MIN / INT_MAX and fail the unsigned bounds test below), which keeps
-    // two f64 per step out of the registers live across the gathers
+    // The pixel FMAs deliver 16.16 fixed point in their low dwords (tsdf_pixel.h), so the pixel
+    // leaves the f64 domain at once: rounding, boundary margin, image bounds and the gather index
+    // are 32-bit and packed 16-bit integer work on one register per step
     double zc[NZ];
-    int iu[NZ], iv[NZ];
-    unsigned long long in[NZ], slow[NZ], any_slow = 0;  // lane masks (fcmp64_mask)
+    unsigned long long cand[NZ], slow[NZ], any_slow = 0;  // lane masks
+    unsigned pix[NZ];
 #pragma unroll
     for (int k = 0; k < NZ; ++k) {
         const double pz = NZ < 8 ? pzs[k % kPz] : readlane_f64(pz_l, k + zoff);
@@ -639,24 +636,23 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
     for (int k = 0; k < NZ; ++k) {
         const double pz = NZ < 8 ? pzs[k % kPz] : readlane_f64(pz_l, k + zoff);
         const double z = zc[k], rz = rzs[k];
-        // X*rz + cx with X = x*fx up to the folding error: within |u - cx| * 2^-24.3 + E/z of
+        // X*rz + C with X = x*fx up to the folding error: within |u - cx| * 2^-24.3 + E/z of
         // the reference's (x*fx)/z + cx, inside the frame_margin boundary margin below where
         // z > zmin (E/z < margin/4; the high-dword integer test is a conservative z > zmin)
-        const double sx = fma(fma(fr.Tf[2], pz, b0), rz, fr.cx), sy = fma(fma(fr.Tf[6], pz, b1), rz, fr.cy);
-        const double ux = rint(sx), uy = rint(sy);
-        // (a NaN fails both tests and takes the exact path; far-out |s| may round differently
-        // but is invalid either way)
-        // fine: z > zmin (so z > 0; the high-dword test passes a positive NaN, which then fails
-        // the pixel tests) and both pixel coordinates clear of a rounding boundary.  The other
-        // steps of the column (rare: near a boundary, at or behind the camera plane) take the
-        // z > 0 test and, where it holds, the exact path below
-        const unsigned long long fine = fcmp64_mask(fabs(sx - ux), fr.half_m, kCmpOLT) &
-                                        fcmp64_mask(fabs(sy - uy), fr.half_m, kCmpOLT) &
+        const double tx = fma(fma(fr.Tf[2], pz, b0), rz, fr.Cx), ty = fma(fma(fr.Tf[6], pz, b1), rz, fr.Cy);
+        const unsigned lx = (unsigned)__double_as_longlong(tx), ly = (unsigned)__double_as_longlong(ty);
+        const unsigned P = __builtin_amdgcn_perm(ly, lx, 0x05040100u);  // (ly.lo, lx.lo): past the boundary, + m
+        const unsigned Q = __builtin_amdgcn_perm(ly, lx, 0x07060302u);  // (ly.hi, lx.hi) = (iv, iu) mod 65536
+        // fine: z > zmin (so z > 0 and, the frame's rows being finite -- else zmin_hi is INT_MAX --
+        // tx, ty are finite, in [2^36, 2^37) and their 16-bit pixel fields do not alias) and both
+        // coordinates clear of a rounding boundary.  The other steps of the column (rare: near a
+        // boundary, near or behind the camera plane) take the z > 0 test and, where it holds,
+        // the exact path below
+        const unsigned long long fine = icmp32_mask(pk_min_u16(P, fr.mm), fr.mm, kCmpEQ) &
                                         icmp32_mask((unsigned)(__double_as_longlong(z) >> 32), (unsigned)fr.zmin_hi, kCmpSGT);
         const unsigned long long col = k < nz ? colm : 0ull;
-        in[k] = col & fine;
-        iu[k] = cvt_i32_sat(ux);
-        iv[k] = cvt_i32_sat(uy);
+        cand[k] = col & fine & icmp32_mask(pk_min_u16(Q, fr.whm1), Q, kCmpEQ);
+        pix[k] = lane_in(cand[k]) ? dot2_u16(Q, fr.wmul) : 0u;
         slow[k] = col & ~fine;  // (z > 0 still to test)
         any_slow |= slow[k];
     }
@@ -665,30 +661,29 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
         TSDF_DDIAG(3);
         const double a0 = fma(fr.T[1], py, fr.T[0] * px);  // the reference's x / y chains
         const double a1 = fma(fr.T[5], py, fr.T[4] * px);
+        const int W = fr.W, H = fr.H;
 #pragma unroll
         for (int k = 0; k < NZ; ++k) {
             slow[k] &= fcmp64_mask(zc[k], 0.0, kCmpOGT);
-            in[k] |= slow[k];
-            if (!slow[k] || !lane_in(slow[k])) continue;
-            TSDF_DDIAG(2);
-            const double pz = NZ < 8 ? pzs[k % kPz] : readlane_f64(pz_l, k + zoff);
-            const double x = fr.T[3] + fma(fr.T[2], pz, a0);
-            const double y = fr.T[7] + fma(fr.T[6], pz, a1);
-            iu[k] = cvt_i32_sat(rint((x * fr.fx) / zc[k] + fr.cx));  // the reference's own operation order
-            iv[k] = cvt_i32_sat(rint((y * fr.fy) / zc[k] + fr.cy));
+            if (!slow[k]) continue;
+            if (lane_in(slow[k])) {
+                TSDF_DDIAG(2);
+                const double pz = NZ < 8 ? pzs[k % kPz] : readlane_f64(pz_l, k + zoff);
+                const double x = fr.T[3] + fma(fr.T[2], pz, a0);
+                const double y = fr.T[7] + fma(fr.T[6], pz, a1);
+                const int iu = cvt_i32_sat(rint((x * fr.fx) / zc[k] + fr.cx));  // the reference's own operation order
+                const int iv = cvt_i32_sat(rint((y * fr.fy) / zc[k] + fr.cy));
+                // unsigned bounds on the saturated indices (they come from integral, non-NaN
+                // values wherever z > 0: the exact path yields NaN only for a non-finite pose,
+                // whose z -- np.linalg.inv: all NaN -- fails z > 0).  The index itself, not the
+                // packed pair, so that images of any accepted size (sides < 2^24, < 2^28 pixels)
+                // pass here; ~0 marks a pixel outside
+                const bool inb = (unsigned)iu < (unsigned)W && (unsigned)iv < (unsigned)H;
+                pix[k] = inb ? __umul24((unsigned)iv, (unsigned)W) + (unsigned)iu : ~0u;
+            }
+            cand[k] |= slow[k] & icmp32_mask(pix[k], ~0u, kCmpNE);
+            pix[k] = lane_in(cand[k]) ? pix[k] : 0u;
         }
-    }
-    unsigned long long cand[NZ];
-    unsigned pix[NZ];
-    const int W = fr.W, H = fr.H;
-#pragma unroll
-    for (int k = 0; k < NZ; ++k) {
-        // unsigned bounds on the saturated indices (they come from integral, non-NaN values
-        // wherever z > 0: the exact path yields NaN only for a non-finite pose, whose z --
-        // np.linalg.inv: all NaN -- fails z > 0)
-        cand[k] = in[k] & icmp32_mask((unsigned)iu[k], (unsigned)W, kCmpULT) &
-                  icmp32_mask((unsigned)iv[k], (unsigned)H, kCmpULT);
-        pix[k] = lane_in(cand[k]) ? __umul24((unsigned)iv[k], (unsigned)W) + (unsigned)iu[k] : 0u;  // v_mad_u32_u24
     }
     // phase 2: gather depth and colour for every step at once, before the depth test, so
     // all the gathers share one memory latency (non-candidates read pixel 0, discarded).  The
@@ -715,8 +710,9 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
 #pragma unroll
     for (int k = 0; k < NZ; ++k) {
         diff[k] = dep[k] - zc[k];
-        // u16: RN(m / 1000) > 0 iff m > 0
-        const unsigned long long dpos = DK != 1 ? icmp32_mask(draw[k], 0u, kCmpNE) : fcmp64_mask(dep[k], 0.0, kCmpOGT);
+        // u16: RN(m / 1000) > 0 iff m > 0.  Texels: an invalid depth is the prep's sentinel, about
+        // -2.1e6 m, and fails the truncation test by itself (every candidate has z > 0)
+        const unsigned long long dpos = DK == 2 ? ~0ull : DK == 0 ? icmp32_mask(draw[k], 0u, kCmpNE) : fcmp64_mask(dep[k], 0.0, kCmpOGT);
         okm[k] = cand[k] & dpos & fcmp64_mask(diff[k], -trunc, kCmpOGE);
     }
 }
@@ -1741,8 +1737,9 @@ __device__ inline void prep_vec_tile(const Batch& bt, unsigned int* count, int t
                                             (b >> 16) | ((cc & 0xFFu) << 16), cc >> 8);
                 if (DK == 2) {  // 8-byte texels (depth, colour)
                     uint4* t = (uint4*)((uint2*)fr.rgbx + p);
-                    t[0] = make_uint4(dd.x & 0xFFFFu, c4.x, dd.x >> 16, c4.y);
-                    t[1] = make_uint4(dd.y & 0xFFFFu, c4.z, dd.y >> 16, c4.w);
+                    const auto dw = [](unsigned d) { return d ? d : TSDF_TEXEL_INVALID; };  // (phase 3 of project_part)
+                    t[0] = make_uint4(dw(dd.x & 0xFFFFu), c4.x, dw(dd.x >> 16), c4.y);
+                    t[1] = make_uint4(dw(dd.y & 0xFFFFu), c4.z, dw(dd.y >> 16), c4.w);
                 } else {
                     *(uint4*)((unsigned*)fr.rgbx + p) = c4;
                 }

@@ -103,6 +103,8 @@ struct Base {
     static constexpr long long kTexelMinBricksDense = 3ll << 14, kTexelMinBricksHash = 3ll << 15;
     bool texel_for(int dk, long long owned_bricks, long long min_bricks) const {
         if (dk != TSDF_DEPTH_U16_MM) return false;
+        // (a texel's invalid depth fails the truncation test by its value, tsdf_pixel.h)
+        if (!(vol.trunc < TSDF_TEXEL_MAX_TRUNC)) return false;
         return texel_mode >= 0 ? texel_mode != 0 : owned_bricks >= min_bricks;
     }
     // deferred f64-metre frames that are all RN(k / 1000) staged as u16 millimetres (defer_push;
