@@ -94,6 +94,21 @@ typedef struct {
     double t_norm;
 } tsdf_track_info_t;
 
+/* The photometric term of the RGB-D entry points.  The defaults of the Python
+ * wrappers: 0.001 m per level, 40 levels. */
+typedef struct {
+    double color_weight;   /* lambda, metres per intensity level: A = A_g + lambda^2 A_c (finite, >= 0;
+                              0: the colour sums are formed and contribute exactly nothing) */
+    float color_max_diff;  /* intensity levels: a pixel whose residual is larger is no colour inlier (> 0) */
+} tsdf_icp_color_params_t;
+
+/* What an RGB-D track reports besides tsdf_track_info_t, of the last linearisation. */
+typedef struct {
+    int64_t color_inliers;     /* colour code 5 */
+    int64_t color_candidates;  /* colour codes 2..5: pixels whose footprint lies inside the model image */
+    double color_rms;          /* sqrt(sum r^2 / color_inliers), intensity levels */
+} tsdf_track_color_info_t;
+
 /* Cumulative counters since create/reset (or the last tsdf_*_stats call with reset != 0). */
 typedef struct {
     int64_t frames;           /* frames integrated */
@@ -269,6 +284,24 @@ int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int hei
                      const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
                      double z_near, double z_far, double z_step, double out_pose[16],
                      tsdf_track_info_t* info, double* trajectory, int flags);
+/* tsdf_dense_track with a photometric term: where the view holds one plane, the
+ * geometry cannot see the two in-plane translations and the rotation about the normal; the colour
+ * can.  color: the frame's RGB8 image, height x width x 3 (a host pointer, or a device pointer with
+ * TSDF_DEVICE_PTRS, like depth).  The raycast at pose_guess also writes the model's colour map; one
+ * prep launch turns both images into intensities I = (77 R + 150 G + 29 B) >> 8 and the model's into
+ * photo texels (I, dI/du, dI/dv, depth); every iteration then adds to the point-to-plane system
+ * color_weight^2 times the system of the residuals I_frame(u, v) - I_model(projection of p), bilinear
+ * in the model image (tsdf_icp_linearize_rgbd's arithmetic).  Lost looks at the geometric inliers and
+ * at the pivots of the combined system.  color_weight = 0 gives tsdf_dense_track's result to the
+ * byte.  info as there; color_info (may be NULL) the colour counts.  TSDF_E_ARG: what
+ * tsdf_dense_track refuses, a NULL color / color_params, color_weight < 0 or not finite,
+ * color_max_diff <= 0 (or NaN), an image smaller than 4 x 4. */
+int tsdf_dense_track_rgbd(tsdf_dense_t* h, const void* depth, int depth_kind, const uint8_t* color,
+                          int height, int width, const double K[9], const double pose_guess[16],
+                          const tsdf_icp_params_t* params, const tsdf_icp_color_params_t* color_params,
+                          double z_near, double z_far, double z_step, double out_pose[16],
+                          tsdf_track_info_t* info, tsdf_track_color_info_t* color_info,
+                          double* trajectory, int flags);
 int tsdf_dense_stats(tsdf_dense_t* h, tsdf_stats_t* out, int reset);
 int tsdf_dense_set_profiling(tsdf_dense_t* h, int on);
 
@@ -352,6 +385,17 @@ int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int heigh
  * linearise and the finish launches summed over the iterations run, ms[4] the launches that
  * fell through after a status was set.  -1 before any such call. */
 int tsdf_track_last_ms(double ms[5], int* iterations);
+/* tsdf_dense_track_rgbd on the table. */
+int tsdf_hash_track_rgbd(tsdf_hash_t* h, const void* depth, int depth_kind, const uint8_t* color,
+                         int height, int width, const double K[9], const double pose_guess[16],
+                         const tsdf_icp_params_t* params, const tsdf_icp_color_params_t* color_params,
+                         double z_near, double z_far, double z_step, double out_pose[16],
+                         tsdf_track_info_t* info, tsdf_track_color_info_t* color_info,
+                         double* trajectory, int flags);
+/* After an RGB-D track with profiling on, tsdf_track_last_ms describes it as it does a geometric
+ * one (ms[2] / ms[3]: the RGB-D linearise and finish), and this gives the prep launch (intensity
+ * image and photo texels), which is in none of those five.  -1 before any such call. */
+int tsdf_track_last_prep_ms(double* ms);
 int tsdf_hash_sync(tsdf_hash_t* h);
 /* sync, then a pool on mapped memory hands the memory above its live blocks back (pool_capacity
  * = live blocks + ~3 %, in whole 8 MB pieces; the live blocks move into fresh mapped ranges by one
@@ -399,6 +443,36 @@ int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, in
                        int Hm, int Wm, const double Km[9], const double model_pose[16],
                        const tsdf_icp_params_t* params, double sums[28], int64_t counts[2],
                        uint8_t* code, float* residual, int flags);
+
+/* One RGB-D linearisation: tsdf_icp_linearize's geometric half -- the same bytes --
+ * and, in the same pass over the frame, the photometric half.  color: the frame's RGB8 image
+ * (Hf x Wf x 3); model_colors: the raycast's colour map (Hm x Wm x 3 u8, at least 4 x 4).
+ * Intensity I = (77 R + 150 G + 29 B) >> 8.  The model's photo texel (I, Gx, Gy, D) at (v, u) has
+ * Gx = (I(v,u+1) - I(v,u-1)) / 2, Gy = (I(v+1,u) - I(v-1,u)) / 2 and D = model_depth(v,u) when the
+ * pixel and its four 4-neighbours lie inside the image and all have depth > 0; otherwise it is
+ * invalid (all zeros).  Per sampled pixel with a depth, p = M V as in the geometric half (no normal
+ * is needed; the last row and column take part) and a colour code -- 0 not sampled or no depth;
+ * 1 p_z <= 0, or with x = fxm (p_x / p_z) + cxm, y alike, x0 = floor(x), y0 = floor(y), not
+ * 1 <= x0 <= Wm - 3 and 1 <= y0 <= Hm - 3; 2 one of the texels (y0 + {0,1}, x0 + {0,1}) invalid;
+ * 3 occluded: |D_b - p_z| > dist_max, every bilinear value being lerp_y(lerp_x(t00, t01),
+ * lerp_x(t10, t11)) with lerp(a, b, t) = a + t (b - a) at tx = x - x0, ty = y - y0; 4 the residual
+ * r = I_frame(u, v) - I_b has |r| > color_max_diff; 5 inlier, with the row J = (p x g, g),
+ * g = (Gx_b fxm / p_z, Gy_b fym / p_z, -(g_x p_x + g_y p_y) / p_z) in the fixed f32 order of §7f
+ * (restated by tests/icp_color_ref.py).  sums[0..27] and counts[0..1] as tsdf_icp_linearize's;
+ * sums[28..55] the same 21 + 6 + 1 sums of the colour rows (not scaled by color_weight), counts[2]
+ * the colour inliers, counts[3] the colour candidates (codes 2..5).  code / residual and
+ * color_code / color_residual (Hf x Wf; the residual in intensity levels, 0 where the code is not
+ * 5) may each be NULL.  Pointers, flags and determinism as tsdf_icp_linearize.  TSDF_E_ARG: what
+ * that call refuses, a NULL color / model_colors / color_params, color_weight < 0 or not finite,
+ * color_max_diff <= 0 (or NaN), a model map smaller than 4 x 4. */
+int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const uint8_t* color, int Hf,
+                            int Wf, const double Kf[9], const double rel_pose[16],
+                            const float* model_depth, const float* model_normals,
+                            const uint8_t* model_colors, int Hm, int Wm, const double Km[9],
+                            const double model_pose[16], const tsdf_icp_params_t* params,
+                            const tsdf_icp_color_params_t* color_params, double sums[56],
+                            int64_t counts[4], uint8_t* code, float* residual, uint8_t* color_code,
+                            float* color_residual, int flags);
 
 /* hash_function over n coordinate triples (host in, host out), computed on the device.  The
  * same arithmetic as the kernels' home-slot computation. */

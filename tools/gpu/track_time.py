@@ -14,7 +14,13 @@ Method: the clock is warmed like bench.py's (300 ms of untimed tracks right befo
 configuration's timed loop); every frame is tracked REPS times, a frame's figure is the median of
 its repeats, and the report gives the median, minimum and maximum over the frames.  The poses found
 are compared with the trajectory's own.  Prints one JSON object.
-    PYTHONPATH=union-thesis-slam_amd python tools/gpu/track_time.py"""
+    PYTHONPATH=union-thesis-slam_amd python tools/gpu/track_time.py
+
+--color measures the photometric term (tsdf_*_track_rgbd) instead of the strides: per
+handle the geometric track and the RGB-D track at stride 1, alternately configured in the same run
+on the same build, the frames' RGB images resident on the device; the RGB-D figures add the prep
+launch (tsdf_track_last_prep_ms), which is part of the total."""
+import argparse
 import contextlib
 import ctypes
 import io
@@ -43,18 +49,28 @@ def summary(v, scale=1e3, digits=1):
             "max": round(scale * max(v), digits)}
 
 
-def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3):
+def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, rgb=None):
+    """rgb: the frames' RGB8 images on the device -- then the RGB-D track is timed (the prep launch
+    as a sixth figure), else the geometric one (prep 0)."""
     Kp = _ffi.ptr(_ffi.f64(K, 9))
     prm = tracking.icp_params(stride=stride)
+    cprm, cinfo = tracking.color_params(), _ffi.TrackColorInfo()
     out, info = np.zeros(16), _ffi.TrackInfo()
 
     def track(f):
-        _ffi.call(f"tsdf_{name}_track", obj._h, depth[f].data_ptr(), _ffi.DEPTH_U16_MM, HW[0], HW[1], Kp,
-                  _ffi.ptr(_ffi.f64(poses[f - 1], 16)), ctypes.byref(prm), 0.0, z_far, VOXEL, _ffi.ptr(out),
-                  ctypes.byref(info), None, _ffi.DEVICE_PTRS)
+        head = (obj._h, depth[f].data_ptr(), _ffi.DEPTH_U16_MM)
+        cam = (HW[0], HW[1], Kp, _ffi.ptr(_ffi.f64(poses[f - 1], 16)), ctypes.byref(prm))
+        prep = ctypes.c_double(0.0)
+        if rgb is None:
+            _ffi.call(f"tsdf_{name}_track", *head, *cam, 0.0, z_far, VOXEL, _ffi.ptr(out), ctypes.byref(info), None,
+                      _ffi.DEVICE_PTRS)
+        else:
+            _ffi.call(f"tsdf_{name}_track_rgbd", *head, rgb[f].data_ptr(), *cam, ctypes.byref(cprm), 0.0, z_far, VOXEL,
+                      _ffi.ptr(out), ctypes.byref(info), ctypes.byref(cinfo), None, _ffi.DEVICE_PTRS)
+            _ffi.call("tsdf_track_last_prep_ms", ctypes.byref(prep))
         ms, it = (ctypes.c_double * 5)(), ctypes.c_int()
         _ffi.call("tsdf_track_last_ms", ms, ctypes.byref(it))
-        return list(ms), it.value
+        return list(ms) + [prep.value], it.value
 
     def cast(f, flags):
         _ffi.call(f"tsdf_{name}_raycast", obj._h, HW[0], HW[1], Kp, _ffi.ptr(_ffi.f64(poses[f - 1], 16)), 0.0, z_far,
@@ -70,13 +86,15 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3):
         track(FIRST + i % TRACKED)
         i += 1
     cols = {k: [] for k in ("raycast", "setup", "linearize_per_iter", "finish_per_iter", "fall_through", "total",
-                            "raycast_share")}
-    iters, status, inliers, err_t, err_r, start_t, start_r = [], [], [], [], [], [], []
+                            "raycast_share", "prep")}
+    iters, status, inliers, c_inliers, err_t, err_r, start_t, start_r = [], [], [], [], [], [], [], []
     for f in frames:
         r = [track(f) for _ in range(REPS)]
         it = r[0][1]
-        med = [float(np.median([x[0][k] for x in r])) for k in range(5)]
+        med = [float(np.median([x[0][k] for x in r])) for k in range(6)]
         total = sum(med)
+        cols["prep"].append(med[5])
+        c_inliers.append(cinfo.color_inliers)
         cols["raycast"].append(med[0])
         cols["setup"].append(med[1])
         cols["linearize_per_iter"].append(med[2] / max(it, 1))
@@ -101,6 +119,8 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3):
     res["iterations"] = {"median": float(np.median(iters)), "min": min(iters), "max": max(iters)}
     res["status"] = {s: status.count(s) for s in sorted(set(status))}
     res["inliers"] = {"median": float(np.median(inliers)), "min": int(min(inliers)), "max": int(max(inliers))}
+    if rgb is not None:
+        res["color_inliers"] = {"median": float(np.median(c_inliers)), "min": int(min(c_inliers)), "max": int(max(c_inliers))}
     res["start_error"] = {"mm": summary(start_t, 1e3, 2), "deg": summary(start_r, 1.0, 3)}
     res["final_error"] = {"mm": summary(err_t, 1e3, 2), "deg": summary(err_r, 1.0, 3)}
     res["warmup_tracks"] = i
@@ -108,6 +128,9 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--color", action="store_true", help="geometric against RGB-D track at stride 1 (see above)")
+    args = ap.parse_args()
     dev = torch.device("cuda", 0)
     poses = scene.trajectory(FRAMES, seed=0, radius_frac=scene.BENCH_RING)
     sph = scene.make_spheres(0, ring_frac=scene.BENCH_RING)
@@ -132,10 +155,12 @@ def main():
                    hash_fusion.HashTable(bnds, VOXEL, 1 << 22, max_blocks=1 << 15))
         obj.integrate_batch(depth.data_ptr(), rgb.data_ptr(), K, Tinv, hw=HW, device_ptrs=True)
         obj.set_profiling(True)
-        for stride in (1, 2):
-            r = time_config(obj, name, K, poses, depth, stride, z_far, maps)
-            res[f"{name}_stride{stride}"] = r
-            print(name, stride, json.dumps(r), file=sys.stderr, flush=True)
+        configs = ([("stride1", 1, None), ("stride2", 2, None)] if not args.color else
+                   [("geometry", 1, None), ("rgbd", 1, rgb), ("geometry_again", 1, None), ("rgbd_again", 1, rgb)])
+        for label, stride, images in configs:
+            r = time_config(obj, name, K, poses, depth, stride, z_far, maps, rgb=images)
+            res[f"{name}_{label}"] = r
+            print(name, label, json.dumps(r), file=sys.stderr, flush=True)
         obj.close()
         torch.cuda.empty_cache()
     print(json.dumps(res))

@@ -21,6 +21,9 @@
 // linearise: a kernel boundary makes the partial records visible across the XCDs' L2s by itself,
 // where a last-arriver protocol needs an agent-scope release per workgroup, a ticket atomic and an
 // acquire, for the price of one more launch of a few microseconds (§7e).
+//
+// With the frame's RGB image a photometric term joins the geometric one (§7f): k_icp_photo_prep,
+// k_icp_linearize_rgbd and k_icp_finish_rgbd below, behind entry points of their own.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -60,15 +63,18 @@ struct IcpCtx {
     int device = 0;
     hipStream_t stream = nullptr;  // the handle's, or the context's own
     bool own_stream = false;
-    void* buf[8] = {};             // see the enum
-    size_t bytes[8] = {};
+    void* buf[14] = {};            // see the enum
+    size_t bytes[14] = {};
     std::mutex mu;
     void release();
 };
-enum { kBufDepth, kBufModelD, kBufModelN, kBufCode, kBufResid, kBufTables, kBufPartial, kBufState };
+enum { kBufDepth, kBufModelD, kBufModelN, kBufCode, kBufResid, kBufTables, kBufPartial, kBufState,
+       // the photometric term (§7f): frame RGB8, model colour map, frame intensity, photo texels, colour code / residual
+       kBufRgb, kBufModelC, kBufFrameI, kBufTexel, kBufCodeC, kBufResidC, kNumBuf };
+static_assert(kNumBuf == 14, "IcpCtx::buf holds one pointer per enumerator");
 
 void IcpCtx::release() {
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kNumBuf; ++i) {
         if (buf[i]) (void)hipFree(buf[i]);
         buf[i] = nullptr;
         bytes[i] = 0;
@@ -371,6 +377,391 @@ __global__ __launch_bounds__(kFinWG) void k_icp_finish(FinishArgs a) {
     a.st->status = status;
 }
 
+// ---- the photometric term ----------------------------------------------------------
+// k_icp_linearize_rgbd does the work of k_icp_linearize (the same operations in the same order: the
+// same bytes) and, in the same pass over the frame, the colour term: the frame's depth is read once
+// and p is shared.  Colour codes:
+//   0 not sampled / no depth     1 behind the model camera or footprint outside its image
+//   2 an invalid texel under the footprint     3 occluded (dist_max)     4 too different (color_max_diff)
+//   5 inlier
+// The partial record doubles: columns 0..31 as k_icp_linearize's, 32..59 the colour sums, 60 / 61 the
+// colour inliers / candidates.  k_icp_finish_rgbd adds each half in k_icp_finish's order, combines
+// them with lambda^2 and solves.  The two geometry-only kernels above are left as they were; what
+// they do is repeated here, not shared, so that their code does not change.
+constexpr int kRgbdRec = 2 * kIcpRec;  // doubles per partial record
+
+struct IcpRecordRgbd {
+    double M[16];
+    double sums[28];     // geometric, as IcpRecord's
+    long long inliers, candidates;
+    double w_norm, t_norm;
+    int status;
+    int pad;
+    double csums[28];    // colour, the same layout (not scaled by lambda^2)
+    long long c_inliers, c_candidates;
+};
+
+struct RgbdArgs {
+    IcpArgs g;
+    const unsigned char* fi;  // Hf x Wf: the frame's intensity
+    const float4* tex;        // Hm x Wm: (I, Gx, Gy, D) of the model, all 0 where invalid
+    float color_max;
+    unsigned char* ccode;
+    float* cresid;
+};
+
+__device__ inline float intensity_u8(const unsigned char* c) {
+    return (float)((77u * c[0] + 150u * c[1] + 29u * c[2]) >> 8);
+}
+
+// Once per call: the frame's intensity image and the model's photo texels.
+__global__ void k_icp_photo_prep(const unsigned char* rgb, int n_frame, unsigned char* fi, const unsigned char* mc,
+                                 const float* dm, int Hm, int Wm, float4* tex) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_frame) fi[i] = (unsigned char)((77u * rgb[3 * (size_t)i] + 150u * rgb[3 * (size_t)i + 1] + 29u * rgb[3 * (size_t)i + 2]) >> 8);
+    if (i >= Hm * Wm) return;
+    const int u = i % Wm, v = i / Wm;
+    float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (u >= 1 && u <= Wm - 2 && v >= 1 && v <= Hm - 2) {
+        const float d = dm[i];
+        if (d > 0.0f && dm[i - 1] > 0.0f && dm[i + 1] > 0.0f && dm[i - Wm] > 0.0f && dm[i + Wm] > 0.0f) {
+            const unsigned char* c = mc + 3 * (size_t)i;
+            t.x = intensity_u8(c);
+            t.y = (intensity_u8(c + 3) - intensity_u8(c - 3)) * 0.5f;
+            t.z = (intensity_u8(c + 3 * (size_t)Wm) - intensity_u8(c - 3 * (size_t)Wm)) * 0.5f;
+            t.w = d;
+        }
+    }
+    tex[i] = t;
+}
+
+__device__ inline float lerpf(float a, float b, float t) { return a + t * (b - a); }
+__device__ inline float bilerp(float t00, float t01, float t10, float t11, float tx, float ty) {
+    return lerpf(lerpf(t00, t01, tx), lerpf(t10, t11, tx), ty);
+}
+
+template <int DK>
+__global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
+    const IcpArgs& a = A.g;
+    if (a.st->status != kIcpRunning) return;
+    float M[12];
+    for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
+    const float dist2 = a.dist_max * a.dist_max;
+
+    double s[56];  // 0..27 geometric, 28..55 colour
+#pragma unroll
+    for (int i = 0; i < 56; ++i) s[i] = 0.0;
+    unsigned n_in = 0, n_cand = 0, c_in = 0, c_cand = 0;
+
+    const long long n = (long long)a.su * a.sv;
+    for (long long i = (long long)blockIdx.x * kIcpWG + threadIdx.x; i < n; i += (long long)gridDim.x * kIcpWG) {
+        const int u = (int)(i % a.su) * a.stride, v = (int)(i / a.su) * a.stride;
+        const size_t pf = (size_t)v * a.Wf + u;
+        int code = 0, cc = 0;
+        float r = 0.0f, J[6], rc = 0.0f, Jc[6];
+        const float d = depth_at<DK>(a, u, v);
+        if (good_depth(d)) {
+            const float xu = a.xf[u], yv = a.yf[v];
+            const float V[3] = {xu * d, yv * d, d};
+            float p[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[k] = ((M[4 * k] * V[0] + M[4 * k + 1] * V[1]) + M[4 * k + 2] * V[2]) + M[4 * k + 3];
+            // the projection both halves start from (the geometric half rounds it, the colour half floors it)
+            const float x = a.fxm * (p[0] / p[2]) + a.cxm, y = a.fym * (p[1] / p[2]) + a.cym;
+            // the geometric half: k_icp_linearize's operations
+            do {
+                if (u >= a.Wf - 1 || v >= a.Hf - 1) break;
+                code = 1;
+                const float dr = depth_at<DK>(a, u + 1, v), dd = depth_at<DK>(a, u, v + 1);
+                if (!good_depth(dr) || !good_depth(dd)) break;
+                const float xr = a.xf[u + 1], yd = a.yf[v + 1];
+                const float Ar[3] = {xr * dr - V[0], yv * dr - V[1], dr - V[2]};
+                const float Bd[3] = {xu * dd - V[0], yd * dd - V[1], dd - V[2]};
+                const float c[3] = {Bd[1] * Ar[2] - Bd[2] * Ar[1], Bd[2] * Ar[0] - Bd[0] * Ar[2], Bd[0] * Ar[1] - Bd[1] * Ar[0]};
+                const float l = __fsqrt_rn((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+                if (l == 0.0f) break;
+                const float nf[3] = {c[0] / l, c[1] / l, c[2] / l};
+                float m[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) m[k] = (M[4 * k] * nf[0] + M[4 * k + 1] * nf[1]) + M[4 * k + 2] * nf[2];
+                code = 2;
+                if (p[2] <= 0.0f) break;
+                const float uf = rintf(x), vf = rintf(y);
+                if (!(uf >= 0.0f && uf <= (float)(a.Wm - 1) && vf >= 0.0f && vf <= (float)(a.Hm - 1))) break;
+                const int um = (int)uf, vm = (int)vf;
+                const size_t pm = (size_t)vm * a.Wm + um;
+                const float dm = a.dm[pm];
+                const float nw[3] = {a.nm[3 * pm], a.nm[3 * pm + 1], a.nm[3 * pm + 2]};
+                code = 3;
+                if (!(dm > 0.0f) || (nw[0] == 0.0f && nw[1] == 0.0f && nw[2] == 0.0f)) break;
+                const float q[3] = {a.xm[um] * dm, a.ym[vm] * dm, dm};
+                float nn[3], e[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    nn[k] = (a.Rm[k] * nw[0] + a.Rm[3 + k] * nw[1]) + a.Rm[6 + k] * nw[2];
+                    e[k] = q[k] - p[k];
+                }
+                code = 4;
+                if ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2] > dist2) break;
+                code = 5;
+                if ((nn[0] * m[0] + nn[1] * m[1]) + nn[2] * m[2] < a.cos_min) break;
+                code = 6;
+                r = (nn[0] * e[0] + nn[1] * e[1]) + nn[2] * e[2];
+                J[0] = p[1] * nn[2] - p[2] * nn[1];
+                J[1] = p[2] * nn[0] - p[0] * nn[2];
+                J[2] = p[0] * nn[1] - p[1] * nn[0];
+                J[3] = nn[0];
+                J[4] = nn[1];
+                J[5] = nn[2];
+            } while (false);
+            // the colour half
+            do {
+                cc = 1;
+                if (p[2] <= 0.0f) break;
+                const float x0 = floorf(x), y0 = floorf(y);
+                if (!(x0 >= 1.0f && x0 <= (float)(a.Wm - 3) && y0 >= 1.0f && y0 <= (float)(a.Hm - 3))) break;
+                const size_t pm = (size_t)(int)y0 * a.Wm + (int)x0;  // rows y0, y0 + 1 <= Hm - 2; columns x0, x0 + 1 <= Wm - 2
+                const float4 t00 = A.tex[pm], t01 = A.tex[pm + 1], t10 = A.tex[pm + a.Wm], t11 = A.tex[pm + a.Wm + 1];
+                cc = 2;
+                if (!(t00.w > 0.0f && t01.w > 0.0f && t10.w > 0.0f && t11.w > 0.0f)) break;
+                const float tx = x - x0, ty = y - y0;
+                const float Db = bilerp(t00.w, t01.w, t10.w, t11.w, tx, ty);
+                cc = 3;
+                if (fabsf(Db - p[2]) > a.dist_max) break;
+                const float Ib = bilerp(t00.x, t01.x, t10.x, t11.x, tx, ty);
+                const float res = (float)A.fi[pf] - Ib;
+                cc = 4;
+                if (fabsf(res) > A.color_max) break;
+                cc = 5;
+                rc = res;
+                const float ga = bilerp(t00.y, t01.y, t10.y, t11.y, tx, ty) * a.fxm;
+                const float gb = bilerp(t00.z, t01.z, t10.z, t11.z, tx, ty) * a.fym;
+                const float iz = 1.0f / p[2];
+                const float gx = ga * iz, gy = gb * iz;
+                const float g[3] = {gx, gy, -((gx * p[0] + gy * p[1]) * iz)};
+                Jc[0] = p[1] * g[2] - p[2] * g[1];
+                Jc[1] = p[2] * g[0] - p[0] * g[2];
+                Jc[2] = p[0] * g[1] - p[1] * g[0];
+                Jc[3] = g[0];
+                Jc[4] = g[1];
+                Jc[5] = g[2];
+            } while (false);
+        }
+        if (code >= 2) ++n_cand;
+        if (code == 6) {
+            ++n_in;
+            int k = 0;
+#pragma unroll
+            for (int x = 0; x < 6; ++x)
+#pragma unroll
+                for (int y = x; y < 6; ++y) s[k++] += (double)J[x] * (double)J[y];
+#pragma unroll
+            for (int x = 0; x < 6; ++x) s[21 + x] += (double)J[x] * (double)r;
+            s[27] += (double)r * (double)r;
+        }
+        if (cc >= 2) ++c_cand;
+        if (cc == 5) {
+            ++c_in;
+            int k = 28;
+#pragma unroll
+            for (int x = 0; x < 6; ++x)
+#pragma unroll
+                for (int y = x; y < 6; ++y) s[k++] += (double)Jc[x] * (double)Jc[y];
+#pragma unroll
+            for (int x = 0; x < 6; ++x) s[49 + x] += (double)Jc[x] * (double)rc;
+            s[55] += (double)rc * (double)rc;
+        }
+        if (a.code) a.code[pf] = (unsigned char)code;
+        if (a.resid) a.resid[pf] = r;
+        if (A.ccode) A.ccode[pf] = (unsigned char)cc;
+        if (A.cresid) A.cresid[pf] = rc;
+    }
+
+    // the wave's butterfly, then the waves in wave order through LDS: as k_icp_linearize
+#pragma unroll
+    for (int i = 0; i < 56; ++i)
+        for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+    for (int o = 32; o > 0; o >>= 1) {
+        n_in += __shfl_xor(n_in, o);
+        n_cand += __shfl_xor(n_cand, o);
+        c_in += __shfl_xor(c_in, o);
+        c_cand += __shfl_xor(c_cand, o);
+    }
+    __shared__ double sh[kIcpWG / 64][kRgbdRec];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 28; ++i) {
+            sh[wave][i] = s[i];
+            sh[wave][kIcpRec + i] = s[28 + i];
+        }
+        sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
+        sh[wave][29] = (double)n_cand;
+        sh[wave][kIcpRec + 28] = (double)c_in;
+        sh[wave][kIcpRec + 29] = (double)c_cand;
+        sh[wave][30] = sh[wave][31] = sh[wave][kIcpRec + 30] = sh[wave][kIcpRec + 31] = 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < kRgbdRec) {
+        double t = sh[0][threadIdx.x];
+        for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
+        a.partial[(size_t)blockIdx.x * kRgbdRec + threadIdx.x] = t;
+    }
+}
+
+struct FinishRgbdArgs {
+    const double* partial;  // n_partial records of kRgbdRec doubles
+    int n_partial;
+    IcpState* st;
+    IcpRecordRgbd* rec;
+    int solve, last;
+    long long min_inliers;
+    double eps_rot, eps_trans;
+    double l2;              // color_weight^2
+};
+
+// A xi = b by Cholesky, E = Rodrigues(w) with translation t, M <- E M: k_icp_finish's arithmetic on
+// the 27 sums in t.  Returns the status; M, w_norm and t_norm change only when the step is taken.
+// Every loop is unrolled so that L, y and xi are never indexed by a variable: they stay in registers
+// (no private segment), where k_icp_finish keeps 304 bytes of it.
+__device__ int icp_solve_update(const double* t, bool enough, int last, double eps_rot, double eps_trans, double* M,
+                                double* w_norm, double* t_norm) {
+    double L[6][6], b[6];
+    int k = 0;
+#pragma unroll
+    for (int x = 0; x < 6; ++x)
+#pragma unroll
+        for (int y = x; y < 6; ++y) L[y][x] = t[k++];
+#pragma unroll
+    for (int x = 0; x < 6; ++x) b[x] = t[21 + x];
+    bool ok = enough;
+#pragma unroll
+    for (int c = 0; c < 6 && ok; ++c) {
+        double d = L[c][c];
+#pragma unroll
+        for (int e = 0; e < c; ++e) d -= L[c][e] * L[c][e];
+        if (!(d > 0.0) || !(d < INFINITY)) {
+            ok = false;
+            break;
+        }
+        d = sqrt(d);
+        L[c][c] = d;
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            double x = L[r][c];
+#pragma unroll
+            for (int e = 0; e < c; ++e) x -= L[r][e] * L[c][e];
+            L[r][c] = x / d;
+        }
+    }
+    if (!ok) return TSDF_TRACK_LOST;
+    double y[6], xi[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double x = b[r];
+#pragma unroll
+        for (int e = 0; e < r; ++e) x -= L[r][e] * y[e];
+        y[r] = x / L[r][r];
+    }
+#pragma unroll
+    for (int r = 5; r >= 0; --r) {
+        double x = y[r];
+#pragma unroll
+        for (int e = r + 1; e < 6; ++e) x -= L[e][r] * xi[e];
+        xi[r] = x / L[r][r];
+    }
+    const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2, th = sqrt(th2);
+    double A = 1.0, Bc = 0.5;
+    if (th > 1e-8) {
+        A = sin(th) / th;
+        Bc = (1.0 - cos(th)) / th2;
+    }
+    const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+    double E[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double k2 = (K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c]) + K[3 * r + 2] * K[6 + c];
+            E[3 * r + c] = ((r == c ? 1.0 : 0.0) + A * K[3 * r + c]) + Bc * k2;
+        }
+    double N[16];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            double x = (E[3 * r] * M[c] + E[3 * r + 1] * M[4 + c]) + E[3 * r + 2] * M[8 + c];
+            if (c == 3) x += xi[3 + r];
+            N[4 * r + c] = x;
+        }
+    N[12] = N[13] = N[14] = 0.0;
+    N[15] = 1.0;
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) finite = finite && N[i] - N[i] == 0.0;
+    if (!finite) return TSDF_TRACK_LOST;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) M[i] = N[i];
+    *w_norm = th;
+    *t_norm = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
+    if (*w_norm <= eps_rot && *t_norm <= eps_trans) return TSDF_TRACK_CONVERGED;
+    return last ? TSDF_TRACK_MAX_ITER : kIcpRunning;
+}
+
+__global__ __launch_bounds__(kFinWG) void k_icp_finish_rgbd(FinishRgbdArgs a) {
+    if (a.st->status != kIcpRunning) return;
+    // lane (slice, j) adds column j of both halves over the records slice, slice + 32, ...; then the
+    // slices in order: each half in exactly k_icp_finish's order of addition
+    __shared__ double sh[kFinSlices][kRgbdRec];
+    __shared__ double tot[kRgbdRec];
+    const int j = threadIdx.x & 31, slice = threadIdx.x >> 5;
+    double tg = 0.0, tc = 0.0;
+    if (j < 30) {
+#pragma unroll 4
+        for (int g = slice; g < a.n_partial; g += kFinSlices) {
+            tg += a.partial[(size_t)g * kRgbdRec + j];
+            tc += a.partial[(size_t)g * kRgbdRec + kIcpRec + j];
+        }
+    }
+    sh[slice][j] = tg;
+    sh[slice][kIcpRec + j] = tc;
+    __syncthreads();
+    if (threadIdx.x < kRgbdRec) {
+        double x = sh[0][threadIdx.x];
+        for (int k = 1; k < kFinSlices; ++k) x += sh[k][threadIdx.x];
+        tot[threadIdx.x] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+
+    IcpRecordRgbd& R = *a.rec;
+    for (int i = 0; i < 28; ++i) {
+        R.sums[i] = tot[i];
+        R.csums[i] = tot[kIcpRec + i];
+    }
+    R.inliers = (long long)tot[28];
+    R.candidates = (long long)tot[29];
+    R.c_inliers = (long long)tot[kIcpRec + 28];
+    R.c_candidates = (long long)tot[kIcpRec + 29];
+    R.w_norm = R.t_norm = 0.0;
+    double M[16];
+    for (int i = 0; i < 16; ++i) M[i] = a.st->M[i];
+    int status = kIcpRunning;
+    if (a.solve) {
+        double t[27];  // A = A_g + lambda^2 A_c, b = b_g + lambda^2 b_c
+        for (int i = 0; i < 27; ++i) t[i] = tot[i] + a.l2 * tot[kIcpRec + i];
+        status = icp_solve_update(t, R.inliers >= a.min_inliers, a.last, a.eps_rot, a.eps_trans, M, &R.w_norm, &R.t_norm);
+    }
+    for (int i = 0; i < 16; ++i) {
+        R.M[i] = M[i];
+        a.st->M[i] = M[i];
+    }
+    R.status = status;
+    a.st->iters += 1;
+    a.st->status = status;
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 int ensure(IcpCtx& c, int which, size_t need) {
     if (need <= c.bytes[which]) return TSDF_OK;
@@ -612,6 +1003,226 @@ int cast_hash(void* h, int H, int W, const double* K, const double* pose, double
     return tsdf_hash_raycast((tsdf_hash_t*)h, H, W, K, pose, zn, zf, zs, d, n, c, flags);
 }
 
+// The per-device context of the handle-less calls (created on first use), with the device made current.
+int device_context(int device, IcpCtx** out, int* n_cu) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(TSDF_E_NODEV, "no HIP device visible");
+    if (device < 0 || device >= ndev || device >= kMaxDev)
+        return set_error(TSDF_E_ARG, "device %d out of range [0,%d)", device, std::min(ndev, kMaxDev));
+    TSDF_HIP(hipSetDevice(device));
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    if (!g_dev_ctx[device]) {
+        IcpCtx* n = new IcpCtx();
+        n->device = device;
+        n->own_stream = true;
+        const hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            delete n;
+            TSDF_HIP(e);
+        }
+        g_dev_ctx[device] = n;
+    }
+    *out = g_dev_ctx[device];
+    *n_cu = 256;
+    (void)hipDeviceGetAttribute(n_cu, hipDeviceAttributeMultiprocessorCount, device);
+    return TSDF_OK;
+}
+
+// ---- the photometric term's host side (§7f) ------------------------------------------------------
+int check_color_params(const tsdf_icp_color_params_t* q) {
+    if (!q) return set_error(TSDF_E_ARG, "null color params pointer");
+    if (!(q->color_weight >= 0.0) || !std::isfinite(q->color_weight))
+        return set_error(TSDF_E_ARG, "color_weight must be finite and >= 0 (got %g)", q->color_weight);
+    if (!(q->color_max_diff > 0.0f)) return set_error(TSDF_E_ARG, "color_max_diff must be > 0 (got %g)", (double)q->color_max_diff);
+    return TSDF_OK;
+}
+
+// From the arguments prepare() made: the wider partial records, the intensity image and the photo
+// texels (one prep launch queued on the stream).  rgb and mc are device pointers.
+int prepare_rgbd(IcpCtx& c, const IcpArgs& a, unsigned grid, int stride, const unsigned char* rgb, const unsigned char* mc,
+                 const tsdf_icp_color_params_t& q, unsigned char* ccode, float* cresid, RgbdArgs* out) {
+    const size_t pf = (size_t)a.Hf * a.Wf, pm = (size_t)a.Hm * a.Wm;
+    TSDF_TRY(ensure(c, kBufFrameI, pf));
+    TSDF_TRY(ensure(c, kBufTexel, pm * sizeof(float4)));
+    TSDF_TRY(ensure(c, kBufPartial, (size_t)grid * kRgbdRec * sizeof(double)));
+    RgbdArgs A{};
+    A.g = a;
+    A.g.partial = (double*)c.buf[kBufPartial];
+    A.fi = (const unsigned char*)c.buf[kBufFrameI];
+    A.tex = (const float4*)c.buf[kBufTexel];
+    A.color_max = q.color_max_diff;
+    A.ccode = ccode;
+    A.cresid = cresid;
+    hipLaunchKernelGGL(k_icp_photo_prep, dim3((unsigned)((std::max(pf, pm) + 255) / 256)), dim3(256), 0, c.stream, rgb, (int)pf,
+                       (unsigned char*)c.buf[kBufFrameI], mc, a.dm, a.Hm, a.Wm, (float4*)c.buf[kBufTexel]);
+    TSDF_HIP(hipGetLastError());
+    if (stride > 1) {
+        if (ccode) TSDF_HIP(hipMemsetAsync(ccode, 0, pf, c.stream));
+        if (cresid) TSDF_HIP(hipMemsetAsync(cresid, 0, pf * sizeof(float), c.stream));
+    }
+    *out = A;
+    return TSDF_OK;
+}
+
+int launch_iteration_rgbd(IcpCtx& c, const RgbdArgs& A, unsigned grid, IcpRecordRgbd* rec, int solve, int last,
+                          const tsdf_icp_params_t& p, double color_weight, hipEvent_t ev_mid = nullptr,
+                          hipEvent_t ev_end = nullptr) {
+    if (A.g.dk == TSDF_DEPTH_U16_MM)
+        hipLaunchKernelGGL(k_icp_linearize_rgbd<TSDF_DEPTH_U16_MM>, dim3(grid), dim3(kIcpWG), 0, c.stream, A);
+    else hipLaunchKernelGGL(k_icp_linearize_rgbd<TSDF_DEPTH_F64_M>, dim3(grid), dim3(kIcpWG), 0, c.stream, A);
+    TSDF_HIP(hipGetLastError());
+    if (ev_mid) TSDF_HIP(hipEventRecord(ev_mid, c.stream));
+    FinishRgbdArgs f{};
+    f.partial = A.g.partial;
+    f.n_partial = (int)grid;
+    f.st = (IcpState*)c.buf[kBufState];
+    f.rec = rec;
+    f.solve = solve;
+    f.last = last;
+    f.min_inliers = p.min_inliers;
+    f.eps_rot = p.eps_rot;
+    f.eps_trans = p.eps_trans;
+    f.l2 = color_weight * color_weight;
+    hipLaunchKernelGGL(k_icp_finish_rgbd, dim3(1), dim3(kFinWG), 0, c.stream, f);
+    TSDF_HIP(hipGetLastError());
+    if (ev_end) TSDF_HIP(hipEventRecord(ev_end, c.stream));
+    return TSDF_OK;
+}
+
+size_t state_bytes_rgbd(int n_rec) { return kRecOff + sizeof(IcpRecordRgbd) * (size_t)n_rec; }
+
+thread_local double g_track_prep_ms = -1.0;  // of the calling thread's last RGB-D track with profiling on
+
+// track() with the colour term: the raycast also writes the model's colour map, one prep launch, and
+// the RGB-D kernels in place of the geometric pair.
+int track_rgbd(const RaySource& S, int (*cast)(void*, int, int, const double*, const double*, double, double, double,
+                                               float*, float*, uint8_t*, int),
+               void* handle, const void* depth, int dk, const uint8_t* color, int H, int W, const double* K,
+               const double* pose_guess, const tsdf_icp_params_t* p, const tsdf_icp_color_params_t* q, double zn,
+               double zf, double zs, double* out_pose, tsdf_track_info_t* info, tsdf_track_color_info_t* cinfo,
+               double* trajectory, int flags) {
+    Base& B = *S.b;
+    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
+    if (!color) return set_error(TSDF_E_ARG, "null color image pointer");
+    if (!K || !pose_guess) return set_error(TSDF_E_ARG, "null camera pointer");
+    if (!out_pose) return set_error(TSDF_E_ARG, "null out_pose pointer");
+    if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
+    if (bad_size(H, W)) return set_error(TSDF_E_ARG, "bad image size %dx%d", H, W);
+    if (H < 4 || W < 4) return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", H, W);
+    TSDF_TRY(check_params(p));
+    TSDF_TRY(check_color_params(q));
+    if (!B.icp) {
+        B.icp = new IcpCtx();
+        B.icp->device = B.device;
+        B.icp->stream = B.stream;
+    }
+    IcpCtx& c = *B.icp;
+    const size_t px = (size_t)H * W;
+    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
+    TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
+    TSDF_TRY(ensure(c, kBufModelC, px * 3));
+    TSDF_TRY(ensure(c, kBufState, state_bytes_rgbd(p->max_iter)));
+    const void* dd = depth;
+    const unsigned char* dc = color;
+    if (!dev) {
+        TSDF_TRY(ensure(c, kBufDepth, frame_bytes_depth(dk, H, W)));
+        TSDF_TRY(ensure(c, kBufRgb, px * 3));
+        dd = c.buf[kBufDepth];
+        dc = (const unsigned char*)c.buf[kBufRgb];
+    }
+    // profiling on: events around the raycast, the setup, the prep and every launch of the iterations
+    const bool timed = B.prof.on;
+    std::vector<hipEvent_t> ev(timed ? 4 + 2 * (size_t)p->max_iter : 0, nullptr);
+    struct EvGuard {
+        std::vector<hipEvent_t>& e;
+        ~EvGuard() {
+            for (auto x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev_guard{ev};
+    for (auto& e : ev) TSDF_HIP(hipEventCreate(&e));
+    if (timed) TSDF_HIP(hipEventRecord(ev[0], c.stream));
+    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN],
+                  (uint8_t*)c.buf[kBufModelC], TSDF_DEVICE_PTRS | TSDF_ASYNC));
+    if (timed) TSDF_HIP(hipEventRecord(ev[1], c.stream));
+    if (!dev) {
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufRgb], color, px * 3, hipMemcpyHostToDevice, c.stream));
+    }
+    char* sb = (char*)c.buf[kBufState];
+    IcpRecordRgbd* rec = (IcpRecordRgbd*)(sb + kRecOff);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)nullptr);
+    TSDF_HIP(hipGetLastError());
+    Cameras cam{H, W, H, W, K, K, pose_guess};
+    IcpArgs a;
+    RgbdArgs A;
+    unsigned grid;
+    TSDF_TRY(prepare(c, cam, *p, dk, flags, dd, (const float*)c.buf[kBufModelD], (const float*)c.buf[kBufModelN], nullptr,
+                     nullptr, B.n_cu, &a, &grid));
+    if (timed) TSDF_HIP(hipEventRecord(ev[2], c.stream));
+    TSDF_TRY(prepare_rgbd(c, a, grid, p->stride, dc, (const unsigned char*)c.buf[kBufModelC], *q, nullptr, nullptr, &A));
+    if (timed) TSDF_HIP(hipEventRecord(ev[3], c.stream));
+    for (int it = 0; it < p->max_iter; ++it)
+        TSDF_TRY(launch_iteration_rgbd(c, A, grid, rec + it, 1, it == p->max_iter - 1, *p, q->color_weight,
+                                       timed ? ev[4 + 2 * it] : nullptr, timed ? ev[5 + 2 * it] : nullptr));
+    std::vector<char> host(state_bytes_rgbd(p->max_iter));
+    TSDF_HIP(hipMemcpyAsync(host.data(), sb, host.size(), hipMemcpyDeviceToHost, c.stream));
+    TSDF_HIP(hipStreamSynchronize(c.stream));
+    const IcpState* st = (const IcpState*)(host.data() + kStateOff);
+    const IcpRecordRgbd* hr = (const IcpRecordRgbd*)(host.data() + kRecOff);
+    const int iters = std::min(std::max(st->iters, 0), p->max_iter);
+    if (timed) {
+        double ms[5] = {0, 0, 0, 0, 0}, prep = 0.0;  // as track()'s, and the prep launch
+        for (size_t i = 0; i + 1 < ev.size(); ++i) {
+            float x = 0.0f;
+            TSDF_HIP(hipEventElapsedTime(&x, ev[i], ev[i + 1]));
+            if (i == 2) {
+                prep += x;
+                continue;
+            }
+            const int it = i < 3 ? 0 : (int)(i - 3) / 2;
+            ms[i < 2 ? i : (it >= iters ? 4 : 2 + (int)(i - 3) % 2)] += x;
+        }
+        for (int i = 0; i < 5; ++i) g_track_ms[i] = ms[i];
+        g_track_ms[5] = (double)iters;
+        g_track_prep_ms = prep;
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) {
+            double x = 0.0;
+            for (int e = 0; e < 4; ++e) x += pose_guess[4 * r + e] * st->M[4 * e + k];
+            out_pose[4 * r + k] = x;
+        }
+    if (info) memset(info, 0, sizeof(*info));
+    if (cinfo) memset(cinfo, 0, sizeof(*cinfo));
+    if (info) {
+        info->status = st->status;
+        info->iterations = iters;
+    }
+    if (iters > 0) {
+        const IcpRecordRgbd& L = hr[iters - 1];
+        if (info) {
+            info->inliers = L.inliers;
+            info->candidates = L.candidates;
+            info->rms = L.inliers > 0 ? std::sqrt(L.sums[27] / (double)L.inliers) : 0.0;
+            info->w_norm = L.w_norm;
+            info->t_norm = L.t_norm;
+        }
+        if (cinfo) {
+            cinfo->color_inliers = L.c_inliers;
+            cinfo->color_candidates = L.c_candidates;
+            cinfo->color_rms = L.c_inliers > 0 ? std::sqrt(L.csums[27] / (double)L.c_inliers) : 0.0;
+        }
+    }
+    if (trajectory) {
+        memset(trajectory, 0, sizeof(double) * 16 * ((size_t)p->max_iter + 1));
+        for (int i = 0; i < 4; ++i) trajectory[5 * i] = 1.0;
+        for (int i = 0; i < iters; ++i) memcpy(trajectory + 16 * (i + 1), hr[i].M, sizeof(double) * 16);
+    }
+    return TSDF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -629,31 +1240,11 @@ int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, in
     if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
     if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
     TSDF_TRY(check_params(params));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_error(TSDF_E_NODEV, "no HIP device visible");
-    if (device < 0 || device >= ndev || device >= kMaxDev)
-        return set_error(TSDF_E_ARG, "device %d out of range [0,%d)", device, std::min(ndev, kMaxDev));
-    TSDF_HIP(hipSetDevice(device));
     IcpCtx* cp;
-    {
-        std::lock_guard<std::mutex> lk(g_dev_mu);
-        if (!g_dev_ctx[device]) {
-            IcpCtx* n = new IcpCtx();
-            n->device = device;
-            n->own_stream = true;
-            const hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
-            if (e != hipSuccess) {
-                delete n;
-                TSDF_HIP(e);
-            }
-            g_dev_ctx[device] = n;
-        }
-        cp = g_dev_ctx[device];
-    }
+    int n_cu;
+    TSDF_TRY(device_context(device, &cp, &n_cu));
     IcpCtx& c = *cp;
     std::lock_guard<std::mutex> lk(c.mu);  // one call at a time per device context
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
     const size_t pf = (size_t)Hf * Wf, pm = (size_t)Hm * Wm;
     TSDF_TRY(ensure(c, kBufState, state_bytes(1)));
@@ -716,6 +1307,116 @@ int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int heigh
     TSDF_TRY(hash_ray_source(h, &S));
     return track(S, cast_hash, h, depth, depth_kind, height, width, K, pose_guess, params, z_near, z_far, z_step, out_pose,
                  info, trajectory, flags);
+}
+
+int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const uint8_t* color, int Hf, int Wf,
+                            const double Kf[9], const double rel_pose[16], const float* model_depth,
+                            const float* model_normals, const uint8_t* model_colors, int Hm, int Wm, const double Km[9],
+                            const double model_pose[16], const tsdf_icp_params_t* params,
+                            const tsdf_icp_color_params_t* color_params, double sums[56], int64_t counts[4], uint8_t* code,
+                            float* residual, uint8_t* color_code, float* color_residual, int flags) {
+    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
+    if (!color) return set_error(TSDF_E_ARG, "null color image pointer");
+    if (!model_depth || !model_normals || !model_colors) return set_error(TSDF_E_ARG, "null model map pointer");
+    if (!Kf || !Km || !rel_pose || !model_pose) return set_error(TSDF_E_ARG, "null camera pointer");
+    if (!sums || !counts) return set_error(TSDF_E_ARG, "null sums / counts pointer");
+    if (depth_kind != TSDF_DEPTH_U16_MM && depth_kind != TSDF_DEPTH_F64_M)
+        return set_error(TSDF_E_ARG, "bad depth_kind %d", depth_kind);
+    if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
+    if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
+    if (Hm < 4 || Wm < 4) return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", Hm, Wm);
+    TSDF_TRY(check_params(params));
+    TSDF_TRY(check_color_params(color_params));
+    IcpCtx* cp;
+    int n_cu;
+    TSDF_TRY(device_context(device, &cp, &n_cu));
+    IcpCtx& c = *cp;
+    std::lock_guard<std::mutex> lk(c.mu);
+    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    const size_t pf = (size_t)Hf * Wf, pm = (size_t)Hm * Wm;
+    TSDF_TRY(ensure(c, kBufState, state_bytes_rgbd(1)));
+    // host images go through the context's buffers: {caller's pointer, buffer, bytes}
+    struct Img {
+        const void* host;
+        int buf;
+        size_t bytes;
+    };
+    const Img in[5] = {{depth, kBufDepth, frame_bytes_depth(depth_kind, Hf, Wf)}, {color, kBufRgb, pf * 3},
+                       {model_depth, kBufModelD, pm * sizeof(float)}, {model_normals, kBufModelN, pm * 3 * sizeof(float)},
+                       {model_colors, kBufModelC, pm * 3}};
+    const Img outs[4] = {{code, kBufCode, pf}, {residual, kBufResid, pf * sizeof(float)}, {color_code, kBufCodeC, pf},
+                         {color_residual, kBufResidC, pf * sizeof(float)}};
+    const void* din[5];
+    void* dout[4];
+    for (int i = 0; i < 5; ++i) {
+        din[i] = in[i].host;
+        if (dev) continue;
+        TSDF_TRY(ensure(c, in[i].buf, in[i].bytes));
+        TSDF_HIP(hipMemcpyAsync(c.buf[in[i].buf], in[i].host, in[i].bytes, hipMemcpyHostToDevice, c.stream));
+        din[i] = c.buf[in[i].buf];
+    }
+    for (int i = 0; i < 4; ++i) {
+        dout[i] = const_cast<void*>(outs[i].host);
+        if (dev || !outs[i].host) continue;
+        TSDF_TRY(ensure(c, outs[i].buf, outs[i].bytes));
+        dout[i] = c.buf[outs[i].buf];
+    }
+    char* sb = (char*)c.buf[kBufState];
+    TSDF_HIP(hipMemcpyAsync(sb + kPoseOff, rel_pose, sizeof(double) * 16, hipMemcpyHostToDevice, c.stream));
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)(sb + kPoseOff));
+    TSDF_HIP(hipGetLastError());
+    Cameras cam{Hf, Wf, Hm, Wm, Kf, Km, model_pose};
+    IcpArgs a;
+    RgbdArgs A;
+    unsigned grid;
+    TSDF_TRY(prepare(c, cam, *params, depth_kind, flags, din[0], (const float*)din[2], (const float*)din[3],
+                     (unsigned char*)dout[0], (float*)dout[1], n_cu, &a, &grid));
+    TSDF_TRY(prepare_rgbd(c, a, grid, params->stride, (const unsigned char*)din[1], (const unsigned char*)din[4],
+                          *color_params, (unsigned char*)dout[2], (float*)dout[3], &A));
+    TSDF_TRY(launch_iteration_rgbd(c, A, grid, (IcpRecordRgbd*)(sb + kRecOff), 0, 1, *params, color_params->color_weight));
+    IcpRecordRgbd rec;
+    TSDF_HIP(hipMemcpyAsync(&rec, sb + kRecOff, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
+    if (!dev)
+        for (int i = 0; i < 4; ++i)
+            if (outs[i].host) TSDF_HIP(hipMemcpyAsync(const_cast<void*>(outs[i].host), dout[i], outs[i].bytes, hipMemcpyDeviceToHost, c.stream));
+    TSDF_HIP(hipStreamSynchronize(c.stream));
+    memcpy(sums, rec.sums, sizeof(double) * 28);
+    memcpy(sums + 28, rec.csums, sizeof(double) * 28);
+    counts[0] = rec.inliers;
+    counts[1] = rec.candidates;
+    counts[2] = rec.c_inliers;
+    counts[3] = rec.c_candidates;
+    return TSDF_OK;
+}
+
+int tsdf_dense_track_rgbd(tsdf_dense_t* h, const void* depth, int depth_kind, const uint8_t* color, int height, int width,
+                          const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                          const tsdf_icp_color_params_t* color_params, double z_near, double z_far, double z_step,
+                          double out_pose[16], tsdf_track_info_t* info, tsdf_track_color_info_t* color_info,
+                          double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return track_rgbd(S, cast_dense, h, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+                      z_far, z_step, out_pose, info, color_info, trajectory, flags);
+}
+
+int tsdf_hash_track_rgbd(tsdf_hash_t* h, const void* depth, int depth_kind, const uint8_t* color, int height, int width,
+                         const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                         const tsdf_icp_color_params_t* color_params, double z_near, double z_far, double z_step,
+                         double out_pose[16], tsdf_track_info_t* info, tsdf_track_color_info_t* color_info,
+                         double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return track_rgbd(S, cast_hash, h, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+                      z_far, z_step, out_pose, info, color_info, trajectory, flags);
+}
+
+int tsdf_track_last_prep_ms(double* ms) {
+    if (!ms) return set_error(TSDF_E_ARG, "null pointer");
+    *ms = g_track_prep_ms;
+    return TSDF_OK;
 }
 
 int tsdf_track_last_ms(double ms[5], int* iterations) {

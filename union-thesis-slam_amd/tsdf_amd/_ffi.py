@@ -77,6 +77,19 @@ class TrackInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class IcpColorParams(ctypes.Structure):
+    """tsdf_icp_color_params_t"""
+    _fields_ = [("color_weight", ctypes.c_double), ("color_max_diff", ctypes.c_float)]
+
+
+class TrackColorInfo(ctypes.Structure):
+    """tsdf_track_color_info_t"""
+    _fields_ = [("color_inliers", ctypes.c_int64), ("color_candidates", ctypes.c_int64), ("color_rms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ICP_MAX_ITER = 64
 TRACK_STATUS = {1: "converged", 2: "max_iter", 3: "lost"}
 
@@ -135,6 +148,10 @@ SIGNATURES = {
     "tsdf_dense_track": [_P, _P, _I, _I, _I, _P, _P, _P, _D, _D, _D, _P, _P, _P, _I],
     "tsdf_hash_track": [_P, _P, _I, _I, _I, _P, _P, _P, _D, _D, _D, _P, _P, _P, _I],
     "tsdf_track_last_ms": [_P, _P],
+    "tsdf_icp_linearize_rgbd": [_I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_dense_track_rgbd": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _I],
+    "tsdf_hash_track_rgbd": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _I],
+    "tsdf_track_last_prep_ms": [_P],
 }
 
 _lib = None

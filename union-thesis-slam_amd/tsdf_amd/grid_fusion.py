@@ -329,7 +329,7 @@ class TSDFVolume:
 
     def track(self, depth_im, cam_intr, pose_guess, *, dist_max=0.1, angle_max_deg=30.0, stride=1, max_iter=10,
               min_inliers=100, eps_rot=1e-5, eps_trans=1e-5, z_near=0.0, z_far=None, z_step=None,
-              return_info=False, invalid_65535=False):
+              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0):
         """The camera pose of a depth frame, tracked against the fused model (tsdf_dense_track,
         DESIGN.md §7e): point-to-plane ICP of depth_im (H,W; uint16 millimetres or metres, as
         integrate() takes it) against this volume's raycast at pose_guess (camera-to-world), both
@@ -339,11 +339,19 @@ class TSDFVolume:
         (pose = pose_guess @ M_last).  A pair is an inlier within dist_max metres and
         angle_max_deg between the normals; every stride-th pixel of every stride-th row is used;
         z_near / z_far / z_step are the raycast's.  The tracking loop:
-            pose = vol.track(depth, K, last_pose); vol.integrate(rgb, depth, K, pose)"""
+            pose = vol.track(depth, K, last_pose); vol.integrate(rgb, depth, K, pose)
+        With color_im, the frame's (H,W,3) uint8 image (a NumPy array, or a CUDA tensor alongside a
+        CUDA depth tensor; anything else raises ValueError), a photometric term joins the geometric
+        one (tsdf_dense_track_rgbd): the frame's intensity against the model's
+        raycast colour map, weighted by color_weight (metres per intensity level; 0 reproduces the
+        geometric track to the byte), residuals above color_max_diff levels rejected.  It observes
+        the motions a view of one plane leaves free.  The info then also has color_inliers,
+        color_candidates and color_rms."""
         from . import tracking
         return tracking.track_call("tsdf_dense_track", self._h, self._vol_bnds, self._voxel_size, depth_im, cam_intr,
                                    pose_guess, dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot,
-                                   eps_trans, z_near, z_far, z_step, return_info, invalid_65535)
+                                   eps_trans, z_near, z_far, z_step, return_info, invalid_65535, color_im,
+                                   color_weight, color_max_diff)
 
     def get_point_cloud(self):
         """grid_fusion.py:322-338: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""

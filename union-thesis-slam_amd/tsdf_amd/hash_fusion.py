@@ -301,12 +301,13 @@ class HashTable:
 
     def track(self, depth_im, cam_intr, pose_guess, *, dist_max=0.1, angle_max_deg=30.0, stride=1, max_iter=10,
               min_inliers=100, eps_rot=1e-5, eps_trans=1e-5, z_near=0.0, z_far=None, z_step=None,
-              return_info=False, invalid_65535=False):
+              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0):
         """As TSDFVolume.track, against the table's raycast (tsdf_hash_track)."""
         from . import tracking
         return tracking.track_call("tsdf_hash_track", self._h, self._vol_bounds, self._voxel_size, depth_im, cam_intr,
                                    pose_guess, dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot,
-                                   eps_trans, z_near, z_far, z_step, return_info, invalid_65535)
+                                   eps_trans, z_near, z_far, z_step, return_info, invalid_65535, color_im,
+                                   color_weight, color_max_diff)
 
     def get_mesh(self):
         """hash_fusion.py:465-484: marching cubes of the densified volume, on the device."""

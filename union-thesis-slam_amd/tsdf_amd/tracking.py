@@ -6,6 +6,8 @@ from files): frame-to-model point-to-plane ICP on the device.
     stream with one synchronisation at the end (tsdf_dense_track / tsdf_hash_track).
   * `icp_linearize`: one linearisation against model maps the caller holds (tsdf_icp_linearize),
     for tests and for trackers that keep their own loop.
+  * With a colour image (`track(color_im=...)`, `icp_linearize_rgbd`) a photometric term joins the
+    geometric one: it observes the motions a single plane leaves free.
 """
 from __future__ import annotations
 
@@ -52,10 +54,38 @@ def _depth_tensor_kind(t):
     return kinds[t.dtype], tuple(kinds)
 
 
+COLOR_WEIGHT, COLOR_MAX_DIFF = 0.001, 40.0  # the wrappers' defaults of the photometric term
+
+
+def color_params(color_weight=COLOR_WEIGHT, color_max_diff=COLOR_MAX_DIFF):
+    """tsdf_icp_color_params_t from the wrappers' keywords."""
+    return _ffi.IcpColorParams(float(color_weight), float(color_max_diff))
+
+
+def _color_image(color_im, name, hw, like_tensor, device):
+    """The address of an (H,W,3) uint8 image: a CUDA tensor read in place when the depth frame is
+    one, else a NumPy array (returned as well, to keep it alive).  Anything else is a ValueError."""
+    if like_tensor:
+        import torch
+        if not _is_tensor(color_im):
+            raise ValueError(f"{name} must be a CUDA tensor when the depth frame is one")
+        return _device_image(color_im, name, tuple(hw) + (3,), (torch.uint8,), device), color_im
+    if _is_tensor(color_im):
+        raise ValueError(f"{name} is a tensor but the depth frame is an array: pass both alike")
+    c = np.asarray(color_im)
+    if c.dtype != np.uint8 or c.shape != tuple(hw) + (3,):
+        raise ValueError(f"{name} must be an (H,W,3) uint8 image of the depth frame's size {tuple(hw)}, "
+                         f"got {c.dtype} {c.shape}")
+    c = np.ascontiguousarray(c)
+    return _ffi.ptr(c), c
+
+
 def track_call(fn, handle, vol_bnds, voxel_size, depth_im, cam_intr, pose_guess, dist_max, angle_max_deg, stride,
-               max_iter, min_inliers, eps_rot, eps_trans, z_near, z_far, z_step, return_info, invalid_65535=False):
-    """The track entry points' host side (tsdf_dense_track / tsdf_hash_track): defaults, the depth
-    frame through encode_depth (or a CUDA tensor read in place), the result as arrays."""
+               max_iter, min_inliers, eps_rot, eps_trans, z_near, z_far, z_step, return_info, invalid_65535=False,
+               color_im=None, color_weight=COLOR_WEIGHT, color_max_diff=COLOR_MAX_DIFF):
+    """The track entry points' host side (tsdf_dense_track / tsdf_hash_track, and with color_im the
+    _rgbd ones): defaults, the depth frame through encode_depth (or a CUDA tensor read in place),
+    the result as arrays."""
     pose = _ffi.f64(pose_guess, 16)
     K = _ffi.f64(cam_intr, 9)
     if z_step is None:
@@ -81,12 +111,24 @@ def track_call(fn, handle, vol_bnds, voxel_size, depth_im, cam_intr, pose_guess,
     info = _ffi.TrackInfo()
     n_traj = max(int(max_iter), 0) + 1
     traj = np.zeros((n_traj, 4, 4), np.float64) if return_info else None
-    _ffi.call(fn, handle, dptr, dk, int(H), int(W), _ffi.ptr(K), _ffi.ptr(pose), ctypes.byref(prm), float(z_near),
-              float(z_far), float(z_step), _ffi.ptr(out), ctypes.byref(info), _ffi.ptr(traj), flags)
+    cinfo = None
+    if color_im is None:
+        _ffi.call(fn, handle, dptr, dk, int(H), int(W), _ffi.ptr(K), _ffi.ptr(pose), ctypes.byref(prm), float(z_near),
+                  float(z_far), float(z_step), _ffi.ptr(out), ctypes.byref(info), _ffi.ptr(traj), flags)
+    else:
+        is_t = _is_tensor(depth_im)
+        cptr, keep = _color_image(color_im, "color_im", (H, W), is_t, depth_im.device.index if is_t else None)
+        cprm, cinfo = color_params(color_weight, color_max_diff), _ffi.TrackColorInfo()
+        _ffi.call(fn + "_rgbd", handle, dptr, dk, cptr, int(H), int(W), _ffi.ptr(K), _ffi.ptr(pose), ctypes.byref(prm),
+                  ctypes.byref(cprm), float(z_near), float(z_far), float(z_step), _ffi.ptr(out), ctypes.byref(info),
+                  ctypes.byref(cinfo), _ffi.ptr(traj), flags)
+        del keep
     out = out.reshape(4, 4)
     if not return_info:
         return out
     res = info.as_dict()
+    if cinfo is not None:
+        res.update(cinfo.as_dict())
     res["status"] = _ffi.TRACK_STATUS.get(info.status, str(info.status))
     res["trajectory"] = traj[:info.iterations + 1].copy()
     return out, res
@@ -150,3 +192,76 @@ def icp_linearize(depth, frame_intr, rel_pose, model_depth, model_normals, model
             k += 1
     return {"sums": sums, "inliers": int(counts[0]), "candidates": int(counts[1]), "A": A, "b": sums[21:27].copy(),
             "code": code, "residual": res}
+
+
+def icp_linearize_rgbd(depth, color, frame_intr, rel_pose, model_depth, model_normals, model_colors, model_intr,
+                       model_pose, *, dist_max=0.1, angle_max_deg=30.0, cos_min=None, stride=1,
+                       color_weight=COLOR_WEIGHT, color_max_diff=COLOR_MAX_DIFF, codes=True, residuals=True,
+                       invalid_65535=False, device=0):
+    """One RGB-D linearisation (tsdf_icp_linearize_rgbd): icp_linearize's geometric
+    half -- the same bytes -- and the photometric half in the same pass.  color (Hf,Wf,3) uint8 is
+    the frame's image, model_colors (Hm,Wm,3) uint8 the raycast's colour map; all images are NumPy
+    arrays or all contiguous CUDA tensors on `device`.  Returns icp_linearize's dict (sums (28,), A, b,
+    inliers, candidates, code, residual: the geometry) plus color_sums (28,), color_A, color_b,
+    color_inliers, color_candidates, color_code (Hf,Wf) u8 (0 .. 5) and color_residual (Hf,Wf) f32
+    in intensity levels.  color_weight is validated and otherwise unused here: the sums are not
+    scaled."""
+    Kf, Km = _ffi.f64(frame_intr, 9), _ffi.f64(model_intr, 9)
+    M, P = _ffi.f64(rel_pose, 16), _ffi.f64(model_pose, 16)
+    prm = icp_params(dist_max, angle_max_deg, stride, cos_min=cos_min)
+    cprm = color_params(color_weight, color_max_diff)
+    flags = _ffi.DEPTH_INVALID_65535 if invalid_65535 else 0
+    images = (depth, color, model_depth, model_normals, model_colors)
+    tensors = [_is_tensor(x) for x in images]
+    if any(tensors):
+        import torch
+        if not all(tensors):
+            raise ValueError("depth, color and the three model maps must be all CUDA tensors or all arrays")
+        dk, dtypes = _depth_tensor_kind(depth)
+        Hf, Wf = depth.shape
+        if model_depth.dim() != 2:
+            raise ValueError("model_depth must be a 2-d CUDA tensor")
+        Hm, Wm = model_depth.shape
+        dptr = _device_image(depth, "depth", (Hf, Wf), dtypes, device)
+        cptr = _device_image(color, "color", (Hf, Wf, 3), (torch.uint8,), device)
+        mptr = _device_image(model_depth, "model_depth", (Hm, Wm), (torch.float32,), device)
+        nptr = _device_image(model_normals, "model_normals", (Hm, Wm, 3), (torch.float32,), device)
+        mcptr = _device_image(model_colors, "model_colors", (Hm, Wm, 3), (torch.uint8,), device)
+        dev = torch.device("cuda", device)
+        outs = [torch.zeros((Hf, Wf), dtype=t, device=dev) if on else None
+                for t, on in ((torch.uint8, codes), (torch.float32, residuals)) * 2]
+        optr = [None if o is None else o.data_ptr() for o in outs]
+        torch.cuda.synchronize(dev)  # the call runs on a stream of its own
+        flags |= _ffi.DEVICE_PTRS
+    else:
+        dk, d = encode_depth(depth)
+        md = np.ascontiguousarray(model_depth, dtype=np.float32)
+        mn = np.ascontiguousarray(model_normals, dtype=np.float32)
+        if d.ndim != 2 or md.ndim != 2 or mn.shape != md.shape + (3,):
+            raise ValueError("depth (Hf,Wf), model_depth (Hm,Wm) and model_normals (Hm,Wm,3) expected")
+        (Hf, Wf), (Hm, Wm) = d.shape, md.shape
+        cptr, c = _color_image(color, "color", (Hf, Wf), False, None)
+        mcptr, mc = _color_image(model_colors, "model_colors", (Hm, Wm), False, None)
+        outs = [np.zeros((Hf, Wf), t) if on else None for t, on in ((np.uint8, codes), (np.float32, residuals)) * 2]
+        dptr, mptr, nptr = (_ffi.ptr(x) for x in (d, md, mn))
+        optr = [_ffi.ptr(o) for o in outs]
+    sums = np.zeros(56, np.float64)
+    counts = np.zeros(4, np.int64)
+    _ffi.call("tsdf_icp_linearize_rgbd", int(device), dptr, dk, cptr, int(Hf), int(Wf), _ffi.ptr(Kf), _ffi.ptr(M), mptr, nptr,
+              mcptr, int(Hm), int(Wm), _ffi.ptr(Km), _ffi.ptr(P), ctypes.byref(prm), ctypes.byref(cprm), _ffi.ptr(sums),
+              _ffi.ptr(counts), *optr, flags)
+
+    def system(v):
+        A = np.zeros((6, 6))
+        k = 0
+        for i in range(6):
+            for j in range(i, 6):
+                A[i, j] = A[j, i] = v[k]
+                k += 1
+        return A, v[21:27].copy()
+
+    (A, b), (Ac, bc) = system(sums[:28]), system(sums[28:])
+    return {"sums": sums[:28].copy(), "inliers": int(counts[0]), "candidates": int(counts[1]), "A": A, "b": b,
+            "code": outs[0], "residual": outs[1], "color_sums": sums[28:].copy(), "color_inliers": int(counts[2]),
+            "color_candidates": int(counts[3]), "color_A": Ac, "color_b": bc, "color_code": outs[2],
+            "color_residual": outs[3]}
