@@ -33,8 +33,9 @@ def _grad(t):
     return g
 
 
-def extract(tsdf, color, origin, voxel_size):
-    """(verts (N,3) f32 world, normals (N,3) f32, colors (N,3) u8, faces (M,3) i32)."""
+def extract(tsdf, color, origin, voxel_size, table=None):
+    """(verts (N,3) f32 world, normals (N,3) f32, colors (N,3) u8, faces (M,3) i32).  table: a
+    256 x 16 case table to use in place of mc_table.table() (the library's, in the CPU tests)."""
     t = np.ascontiguousarray(tsdf, _F)
     X, Y, Z = t.shape
     inside = t < 0
@@ -68,8 +69,8 @@ def extract(tsdf, color, origin, voxel_size):
     # vertex id of grid edge (voxel, axis)
     vid = np.full(X * Y * Z * 3, -1, np.int64)
     vid[flat] = np.arange(len(flat))
-    tab = mc_table.table()
-    cube = np.zeros((X - 1, Y - 1, Z - 1), np.int64) if min(X, Y, Z) > 1 else np.zeros((0, 0, 0), np.int64)
+    tab = mc_table.table() if table is None else table
+    cube = np.zeros((X - 1, Y - 1, Z - 1), np.int64)  # no cells when a dimension is 1
     for c in range(8):
         ox, oy, oz = c & 1, (c >> 1) & 1, (c >> 2) & 1
         cube |= inside[ox:X - 1 + ox, oy:Y - 1 + oy, oz:Z - 1 + oz].astype(np.int64) << c

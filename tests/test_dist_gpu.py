@@ -82,6 +82,101 @@ def test_shard_meshes_unite_to_the_unsharded_mesh(layout, world):
             gappy.extract_mesh()  # a cyclic shard alone would mesh across its column gaps
 
 
+def _random_parts(layout, world, shape=(29, 13, 10), vs=0.01):
+    """An unsharded volume and its shards, loaded with one random field (set_state, each shard
+    its own rows): four brick columns along x, the last ragged, ambiguous cells on every cap row."""
+    from tsdf_amd import grid_fusion, sharding
+    import mesh_checks as M
+    lo = np.array([0.11, -0.23, 0.57])
+    bnds = np.stack([lo, lo + (np.array(shape) - 0.5) * vs], axis=1)
+    t = M.random_field(0, shape)
+    c = np.random.default_rng(7).integers(0, 1 << 24, size=shape).astype(np.float32)
+    full = grid_fusion.TSDFVolume(bnds.copy(), vs)
+    assert tuple(int(d) for d in full._vol_dim) == shape
+    if layout == "cyclic":
+        parts = [grid_fusion.TSDFVolume(bnds.copy(), vs, shard=(r, world)) for r in range(world)]
+    else:
+        parts = [grid_fusion.TSDFVolume(bnds.copy(), vs, slab=sharding.slab(r, world, shape[0])) for r in range(world)]
+    for v in [full] + parts:
+        v.set_state(t[v.x_index], np.ones((len(v.x_index),) + shape[1:], np.float32), c[v.x_index])
+    return full, parts, t, c
+
+
+@pytest.mark.parametrize("layout,world", [("cyclic", 2), ("cyclic", 3), ("slab", 3)])
+def test_shard_meshes_of_a_random_field_unite_to_the_oracle_mesh(layout, world):
+    """As test_shard_meshes_unite_to_the_unsharded_mesh, on a field where every cell is a
+    surface cell (the lounge data puts hardly any ambiguous cell on a cap row), and the
+    unsharded mesh is the oracle's."""
+    from tsdf_amd import sharding
+    import mc_oracle
+    import mesh_checks as M
+    full, parts, t, c = _random_parts(layout, world)
+    X = t.shape[0]
+    assert sorted(np.concatenate([p.x_index for p in parts]).tolist()) == list(range(X))
+    v, n, col, f, k = full.extract_mesh(keys=True)
+    rv, rn, rc, rf = mc_oracle.extract(t, c, full._vol_origin, full._voxel_size)
+    assert np.array_equal(v.view(np.uint32), rv.view(np.uint32)) and np.array_equal(f, rf)
+    assert np.array_equal(col, rc) and np.abs(n - rn).max() <= 1e-6
+    assert np.array_equal(k, M.edge_keys(t)) and len(f) > 5000
+    M.check_manifold(f, k, t.shape)
+    meshes = []
+    for p in parts:
+        halo = _halo_from(parts, p)
+        pv, pn, pc, pf, pk = p.extract_mesh(halo=halo, global_x=X, keys=True)
+        meshes.append((pv, pf, pn, pc, pk))
+    mv, mf, mn, mc = sharding.merge_meshes(meshes)
+    assert np.array_equal(mv.view(np.uint32), v.view(np.uint32))
+    assert np.array_equal(mn.view(np.uint32), n.view(np.uint32)) and np.array_equal(mc, col)
+    uk = np.unique(np.concatenate([m[4] for m in meshes]))
+    assert np.array_equal(uk, k)
+    assert np.array_equal(_sorted_faces(k, mf), _sorted_faces(k, f))
+    assert sum(len(m[1]) for m in meshes) == len(f)  # every cell owned by exactly one shard
+
+
+def test_mesh_domain_refusals():
+    """mesh_domain / mesh_halo_rows (csrc/tsdf_mesh.hip) refuse a bad halo or extent with
+    TSDF_E_ARG and a message naming the fault, before anything is launched: the handle's last
+    mesh is still there afterwards."""
+    from tsdf_amd import _ffi
+    full, parts, t, c = _random_parts("cyclic", 2)
+    X = t.shape[0]
+    p = parts[0]  # brick columns 0 and 3 (sharding.columns): rows 0-7 and 24-28
+    assert p.x_index.tolist() == list(range(8)) + list(range(24, 29))
+    gx, ht, hc = _halo_from(parts, p)
+    assert gx.tolist() == [8, 9, 23]
+    good = p.extract_mesh(halo=(gx, ht, hc), global_x=X, keys=True)
+    assert len(good[3]) > 1000
+
+    def refused(message, gx_, ht_, hc_, global_x=X):
+        with pytest.raises(_ffi.TSDFError) as ei:
+            p.extract_mesh(halo=(np.asarray(gx_, np.int64), ht_, hc_), global_x=global_x)
+        assert ei.value.code == _ffi.E_ARG and message in str(ei.value), str(ei.value)
+
+    def plus(row):  # the good halo and one more row
+        return np.append(gx, row), np.concatenate([ht, ht[:1]]), np.concatenate([hc, hc[:1]])
+
+    refused("halo row 9 given twice", *plus(9))
+    refused("halo row 24 is a local row", *plus(24))
+    refused("halo row 29 outside [0, 29)", *plus(X))
+    refused("halo row -1 outside [0, 29)", *plus(-1))
+    for drop in range(len(gx)):  # each needed border row left out in turn
+        keep = np.arange(len(gx)) != drop
+        refused("pass the missing border rows", gx[keep], ht[keep], hc[keep])
+    refused("bad global x extent 16777217", gx, ht, hc, global_x=(1 << 24) + 1)
+    with pytest.raises(_ffi.TSDFError) as ei:
+        p.mesh_halo_rows(global_x=20)  # the shard's rows reach x = 28
+    assert ei.value.code == _ffi.E_ARG and "beyond the global extent" in str(ei.value)
+    with pytest.raises(_ffi.TSDFError) as ei:
+        p.mesh_halo_rows(global_x=(1 << 24) + 1)
+    assert ei.value.code == _ffi.E_ARG and "bad global x extent" in str(ei.value)
+    assert p.mesh_halo_rows(global_x=X).tolist() == gx.tolist()
+    # nothing was extracted in between: the handle still holds the good mesh
+    v = np.empty_like(good[0])
+    f = np.empty_like(good[3])
+    _ffi.call("tsdf_dense_get_mesh", p._h, _ffi.ptr(v), None, None, _ffi.ptr(f))
+    assert np.array_equal(v, good[0]) and np.array_equal(f, good[3])
+
+
 def test_slab_alone_meshes_its_sub_volume_in_world_coordinates():
     """A slab meshed without halo is the mesh of its own sub-volume at world positions: every
     vertex has the global key, position and colour of the unsharded mesh's vertex on the same

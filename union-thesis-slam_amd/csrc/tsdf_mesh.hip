@@ -60,6 +60,14 @@ McTable build_table() {
             ++nf;
         }
     }
+    unsigned face_mask[12];  // bit 2 * axis + side: the two cube faces that hold the edge
+    for (int e = 0; e < 12; ++e) {
+        face_mask[e] = 0;
+        for (int axis = 0; axis < 3; ++axis) {
+            const int sa = (corner_pair[e][0] >> axis) & 1, sb = (corner_pair[e][1] >> axis) & 1;
+            if (sa == sb) face_mask[e] |= 1u << (2 * axis + sa);
+        }
+    }
     for (int cfg = 0; cfg < 256; ++cfg) {
         int seg[12];
         for (int i = 0; i < 12; ++i) seg[i] = -1;
@@ -91,10 +99,20 @@ McTable build_table() {
                 left[e] = false;
                 e = seg[e];
             } while (e != start);
+            // fan from the first position whose diagonals all leave the cube's faces: a diagonal
+            // between two crossings of one face lies in that face's plane, where the neighbouring
+            // cell may emit the same edge (a non-manifold edge); such a position always exists
+            int s = 0;
+            for (; s < n; ++s) {
+                bool ok = true;
+                for (int i = 2; i + 1 < n; ++i) ok = ok && !(face_mask[loop[s]] & face_mask[loop[(s + i) % n]]);
+                if (ok) break;
+            }
+            if (s == n) s = 0;  // (never: tests/test_mesh_cpu.py checks every case)
             for (int i = 1; i + 1 < n; ++i) {
-                t.tri[cfg][k++] = (signed char)loop[0];
-                t.tri[cfg][k++] = (signed char)loop[i];
-                t.tri[cfg][k++] = (signed char)loop[i + 1];
+                t.tri[cfg][k++] = (signed char)loop[s];
+                t.tri[cfg][k++] = (signed char)loop[(s + i) % n];
+                t.tri[cfg][k++] = (signed char)loop[(s + i + 1) % n];
             }
         }
         t.ntri[cfg] = (unsigned char)(k / 3);
