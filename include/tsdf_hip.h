@@ -150,6 +150,19 @@ typedef struct {
                                  0: plain allocations grown by copy */
 } tsdf_hash_info_t;
 
+/* The last tsdf_hash_extract_mesh of a table (tsdf_hash_mesh_info). */
+typedef struct {
+    int64_t live_blocks;      /* live blocks inside the volume that the extraction read */
+    int64_t mesh_blocks;      /* block coordinates it meshed: those with a live block among b + {0,1}^3
+                                 (live_blocks <= mesh_blocks <= 8 * live_blocks) */
+    int64_t scratch_bytes;    /* sum of every device allocation it made, the mesh itself included */
+    int64_t n_verts, n_tris;
+} tsdf_hash_mesh_info_t;
+
+/* What tsdf_hash_extract_mesh_fields extracts beside vertices, colours and keys. */
+#define TSDF_MESH_NORMALS 1
+#define TSDF_MESH_FACES 2
+
 const char* tsdf_last_error(void);
 /* Build id of the loaded library: the first 16 hex digits of the sha256 of the sources it was
  * compiled from (csrc/, this header, the Makefile).  Profiles under profiles/ record the id of
@@ -360,9 +373,28 @@ int tsdf_hash_import_blocks(tsdf_hash_t* h, const int32_t* bxyz, int64_t n_block
  * without an entry get tsdf 1, weight 0, colour 0.  Any pointer may be NULL. */
 int tsdf_hash_get_dense(tsdf_hash_t* h, float* tsdf, float* weight, float* color);
 /* The same densify on the device, into a dense handle of the hash's dims (unsharded; it is reset
- * first): get_mesh / get_point_cloud of the hash (hash_fusion.py:465-507) then run the dense
- * handle's marching cubes without a host round trip of the volume. */
+ * first).  The hash's own mesh does not need it (tsdf_hash_extract_mesh); a densified handle's
+ * tsdf_dense_extract_mesh gives the same mesh, at the cost of the whole extent. */
 int tsdf_hash_to_dense(tsdf_hash_t* h, tsdf_dense_t* d);
+/* get_mesh / get_point_cloud of the hash (hash_fusion.py:465-507): marching cubes at level 0 over
+ * the table's live blocks.  The mesh is that of the volume tsdf_hash_get_dense gives
+ * (a voxel without an entry: tsdf 1, colour 0; a slot whose pool block is out of range: absent;
+ * no voxel at or beyond dims) under the rules of tsdf_dense_extract_mesh, and equals the mesh of
+ * the densified handle byte for byte: vertices in increasing key ((x*Y + y)*Z + z)*3 + axis,
+ * triangles in C-order of their anchor cell, then in the case table's order.  Deferred frames run
+ * first.  Memory and work follow the live blocks, the blocks that can hold a vertex or a triangle
+ * (tsdf_hash_mesh_info_t.mesh_blocks) and the mesh -- never dims.  A shard handle (n_shards > 1)
+ * gives the mesh of its own blocks' state.  TSDF_E_ARG for 2^31 or more vertices or triangles
+ * (faces are int32).  The result stays in the handle until the next extract, reset or destroy.
+ * extract_mesh_fields: `fields` (TSDF_MESH_NORMALS | TSDF_MESH_FACES) names what to compute beside
+ * vertices, colours and keys; *n_tris is counted either way.  extract_mesh asks for both.
+ * get_mesh / get_mesh_keys copy it out as tsdf_dense_get_mesh does (any pointer may be NULL);
+ * TSDF_E_ARG for a field that was not extracted. */
+int tsdf_hash_extract_mesh(tsdf_hash_t* h, int64_t* n_verts, int64_t* n_tris);
+int tsdf_hash_extract_mesh_fields(tsdf_hash_t* h, int fields, int64_t* n_verts, int64_t* n_tris);
+int tsdf_hash_get_mesh(tsdf_hash_t* h, float* verts, float* normals, uint8_t* colors, int32_t* faces);
+int tsdf_hash_get_mesh_keys(tsdf_hash_t* h, int64_t* keys);
+int tsdf_hash_mesh_info(tsdf_hash_t* h, tsdf_hash_mesh_info_t* out);
 /* tsdf_dense_raycast on the table: a voxel without an entry has weight 0, as in get_volume.  Absent
  * blocks are skipped by the table alone; each ray keeps the pool blocks of its current 2x2x2 block
  * neighbourhood, so the corner fetches probe only when it leaves that neighbourhood.  The same

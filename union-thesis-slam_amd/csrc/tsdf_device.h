@@ -256,6 +256,24 @@ __device__ inline void coh_store(T* p, T v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The pool block of block (bx, by, bz), or -1: the table's linear probe from the key's home slot
+// (tombstones are stepped over); a slot value outside [0, n_blocks) counts as absent.  For readers
+// of a table no kernel is writing (raycast, mesh).
+__device__ inline int hash_find(const Table& t, int bx, int by, int bz, long long n_blocks) {
+    const unsigned long long key = pack_key(bx, by, bz);
+    long long s = ref_hash(bx, by, bz, t.capacity, t.int_bits);
+    for (long long n = 0; n < t.capacity; ++n) {
+        const unsigned long long k = coh_load(&t.keys[s]);
+        if (k == key) {
+            const int blk = coh_load(&t.vals[s]);
+            return blk >= 0 && blk < n_blocks ? blk : -1;
+        }
+        if (k == kEmpty) return -1;
+        if (++s == t.capacity) s = 0;
+    }
+    return -1;
+}
+
 // World position of a global voxel index (vox2world, grid_fusion.py:170-181):
 // f32( f64(origin_f32) + vs * f64(f32(idx)) ); idx < 2^24 so f32(idx) is exact.
 __device__ inline double vox_world(float origin, double vs, int g) {

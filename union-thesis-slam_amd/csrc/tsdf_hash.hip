@@ -209,6 +209,9 @@ struct tsdf_hash {
     // address ranges of pool arrays that kernels used and that were since compacted away (trim) or
     // replaced by plain allocations: unmapped, but reserved until destroy (VArray::release)
     std::vector<std::pair<char*, size_t>> retired_va;
+    Mesh mesh;  // the last tsdf_hash_extract_mesh (released on reset and destroy)
+    int mesh_fields = 0;
+    tsdf_hash_mesh_info_t mesh_info{};
     int vmm_fail_at = -1;  // test hook (TSDF_HASH_VMM_FAIL=k): the next growth of array k fails
     bool async_grow = true;  // test hook (TSDF_HASH_ASYNC_GROW=0): asynchronous calls never grow ahead
     static constexpr size_t kPer[5] = {sizeof(float) * kBrickVox, sizeof(float) * kBrickVox, sizeof(float) * kBrickVox,
@@ -1435,6 +1438,7 @@ int tsdf_hash_create(const int64_t dims[3], const float origin[3], double voxel_
 int tsdf_hash_destroy(tsdf_hash_t* h) {
     if (!h) return TSDF_OK;
     (void)hipSetDevice(h->b.device);
+    h->mesh.release();
     h->b.release();
     void* ps[] = {h->t.keys, h->t.vals, h->t.overflow, h->t.st, h->d_list, h->d_res, h->d_ins, (void*)h->t.owned};
     for (void* p : ps)
@@ -1459,6 +1463,9 @@ int tsdf_hash_reset(tsdf_hash_t* h) {
     B.touch_state();
     h->pend.on = false;
     TSDF_HIP(hipSetDevice(B.device));
+    h->mesh.release();
+    h->mesh_fields = 0;
+    h->mesh_info = tsdf_hash_mesh_info_t{};
     hipLaunchKernelGGL(k_fill_keys, dim3(2048), dim3(256), 0, B.stream, h->t.keys, h->t.vals,
                        (long long)h->t.capacity);
     TSDF_HIP(hipGetLastError());
@@ -1707,6 +1714,46 @@ int tsdf_hash_to_dense(tsdf_hash_t* h, tsdf_dense_t* d) {
     TSDF_HIP(hipStreamSynchronize(B.stream));
     D.touch_state();
     D.vol.canon = B.vol.canon;
+    return TSDF_OK;
+}
+
+int tsdf_hash_extract_mesh_fields(tsdf_hash_t* h, int fields, int64_t* n_verts, int64_t* n_tris) {
+    if (!h || !n_verts || !n_tris) return set_error(TSDF_E_ARG, "null pointer");
+    if (fields & ~(TSDF_MESH_NORMALS | TSDF_MESH_FACES)) return set_error(TSDF_E_ARG, "unknown mesh fields %d", fields);
+    Base& B = h->b;
+    TSDF_HIP(hipSetDevice(B.device));
+    TSDF_TRY(hash_flush(h));
+    h->mesh_fields = 0;
+    TSDF_TRY(hash_extract_mesh(B, h->t, h->mesh, fields, &h->mesh_info));
+    h->mesh_fields = fields;
+    *n_verts = h->mesh.n_verts;
+    *n_tris = h->mesh.n_tris;
+    return TSDF_OK;
+}
+
+int tsdf_hash_extract_mesh(tsdf_hash_t* h, int64_t* n_verts, int64_t* n_tris) {
+    return tsdf_hash_extract_mesh_fields(h, TSDF_MESH_NORMALS | TSDF_MESH_FACES, n_verts, n_tris);
+}
+
+int tsdf_hash_get_mesh(tsdf_hash_t* h, float* verts, float* normals, uint8_t* colors, int32_t* faces) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    TSDF_HIP(hipSetDevice(h->b.device));
+    if ((normals && !(h->mesh_fields & TSDF_MESH_NORMALS)) || (faces && !(h->mesh_fields & TSDF_MESH_FACES)))
+        return set_error(TSDF_E_ARG, "the last extraction did not compute %s", normals && !(h->mesh_fields & TSDF_MESH_NORMALS) ? "normals" : "faces");
+    if (!h->mesh.verts) return set_error(TSDF_E_ARG, "no mesh extracted");
+    return copy_mesh(h->b, h->mesh, verts, normals, colors, faces);
+}
+
+int tsdf_hash_get_mesh_keys(tsdf_hash_t* h, int64_t* keys) {
+    if (!h || !keys) return set_error(TSDF_E_ARG, "null pointer");
+    TSDF_HIP(hipSetDevice(h->b.device));
+    if (!h->mesh.verts) return set_error(TSDF_E_ARG, "no mesh extracted");
+    return copy_mesh(h->b, h->mesh, nullptr, nullptr, nullptr, nullptr, keys);
+}
+
+int tsdf_hash_mesh_info(tsdf_hash_t* h, tsdf_hash_mesh_info_t* out) {
+    if (!h || !out) return set_error(TSDF_E_ARG, "null pointer");
+    *out = h->mesh_info;
     return TSDF_OK;
 }
 

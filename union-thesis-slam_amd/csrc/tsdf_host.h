@@ -290,6 +290,9 @@ int extract_mesh(Base& B, const Pool& pool, Mesh& m, const MeshDomain& d, const 
 int copy_mesh(Base& B, const Mesh& m, float* verts, float* normals, uint8_t* colors, int32_t* faces,
               int64_t* keys = nullptr);
 
+// The voxel hash's mesher (tsdf_mesh.hip): marching cubes over the table's live blocks.
+int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_mesh_info_t* info);
+
 // The state of a dense handle (tsdf_dense.hip), for the hash's densify into it.
 Base* dense_base(tsdf_dense_t* d);
 

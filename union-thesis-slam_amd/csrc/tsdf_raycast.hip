@@ -71,21 +71,6 @@ struct Hood {
     bool live;     // some block of the neighbourhood holds a voxel with weight > 0 and tsdf < 0
 };
 
-__device__ inline int hash_find(const Table& t, int bx, int by, int bz, long long n_blocks) {
-    const unsigned long long key = pack_key(bx, by, bz);
-    long long s = ref_hash(bx, by, bz, t.capacity, t.int_bits);
-    for (long long n = 0; n < t.capacity; ++n) {
-        const unsigned long long k = coh_load(&t.keys[s]);
-        if (k == key) {
-            const int blk = coh_load(&t.vals[s]);
-            return blk >= 0 && blk < n_blocks ? blk : -1;
-        }
-        if (k == kEmpty) return -1;
-        if (++s == t.capacity) s = 0;
-    }
-    return -1;
-}
-
 // Make the neighbourhood cover the cell at i0 (corners i0 and i0 + 1): kept while
 // 8A <= i0 <= 8A + 14 on every axis, else re-anchored with its room on the side the ray moves to.
 __device__ inline void hood_cover(const RayArgs& a, Hood& h, const int i0[3], const float qd[3]) {

@@ -22,6 +22,7 @@ COLOR_RGB8, COLOR_F32 = 0, 1
 DEVICE_PTRS, ASYNC, DEPTH_INVALID_65535, DEFER, RAY_REFLAG = 1, 2, 4, 8, 16
 
 E_ARG, E_HIP, E_NODEV, E_CAPACITY, E_OOM = -1, -2, -3, -4, -5
+MESH_NORMALS, MESH_FACES = 1, 2  # fields of tsdf_hash_extract_mesh_fields
 
 
 class TSDFError(RuntimeError):
@@ -55,6 +56,15 @@ class HashInfo(ctypes.Structure):
                 ("max_probe", ctypes.c_int64), ("blocks_in_pool", ctypes.c_int64),
                 ("pool_capacity", ctypes.c_int64), ("entries", ctypes.c_int64), ("slots", ctypes.c_int64),
                 ("pool_mapped", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HashMeshInfo(ctypes.Structure):
+    """tsdf_hash_mesh_info_t."""
+    _fields_ = [("live_blocks", ctypes.c_int64), ("mesh_blocks", ctypes.c_int64), ("scratch_bytes", ctypes.c_int64),
+                ("n_verts", ctypes.c_int64), ("n_tris", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -134,6 +144,11 @@ SIGNATURES = {
     "tsdf_hash_frames_per_launch": [_P, _P],
     "tsdf_hash_get_dense": [_P, _P, _P, _P],
     "tsdf_hash_to_dense": [_P, _P],
+    "tsdf_hash_extract_mesh": [_P, _P, _P],
+    "tsdf_hash_extract_mesh_fields": [_P, _I, _P, _P],
+    "tsdf_hash_get_mesh": [_P, _P, _P, _P, _P],
+    "tsdf_hash_get_mesh_keys": [_P, _P],
+    "tsdf_hash_mesh_info": [_P, _P],
     "tsdf_hash_trim": [_P],
     "tsdf_hash_export_blocks": [_P, _P, _P, _P, _P, _P, _P, _I],
     "tsdf_hash_import_blocks": [_P, _P, _I64, _P, _P, _P, _P, _I],

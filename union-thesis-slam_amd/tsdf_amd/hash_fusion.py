@@ -284,7 +284,8 @@ class HashTable:
 
     def _as_grid(self):
         """The densified volume (get_volume, hash_fusion.py:442-463) in a dense device handle,
-        filled on the device from the live blocks (tsdf_hash_to_dense: no host round trip)."""
+        filled on the device from the live blocks (tsdf_hash_to_dense: no host round trip).  Costs
+        the whole extent; get_mesh / get_point_cloud do not use it (extract_mesh)."""
         lo = np.asarray(self._vol_bounds, dtype=np.float64)[:, 0]
         bnds = np.stack([lo, lo + (np.asarray(self._vol_dim) - 0.5) * self._voxel_size], axis=1)  # same dims
         with contextlib.redirect_stdout(io.StringIO()):
@@ -309,13 +310,43 @@ class HashTable:
                                    eps_trans, z_near, z_far, z_step, return_info, invalid_65535, color_im,
                                    color_weight, color_max_diff)
 
+    def extract_mesh(self, normals=True, colors=True, faces=True, keys=False):
+        """Marching cubes at level 0 over the table's live blocks (tsdf_hash_extract_mesh): the
+        mesh of get_state()'s volume, byte for byte what _as_grid().extract_mesh() gives, without
+        a dense volume.  Returns as TSDFVolume.extract_mesh: (verts (N,3) f32 world, normals (N,3)
+        f32, colors (N,3) u8, faces (M,3) i32[, keys (N,) int64]); a field not asked for is None,
+        and normals and faces not asked for are not computed either."""
+        nv, nt = ctypes.c_int64(), ctypes.c_int64()
+        fields = (_ffi.MESH_NORMALS if normals else 0) | (_ffi.MESH_FACES if faces else 0)
+        _ffi.call("tsdf_hash_extract_mesh_fields", self._h, fields, ctypes.byref(nv), ctypes.byref(nt))
+        v = np.empty((nv.value, 3), np.float32)
+        n = np.empty((nv.value, 3), np.float32) if normals else None
+        c = np.empty((nv.value, 3), np.uint8) if colors else None
+        f = np.empty((nt.value, 3), np.int32) if faces else None
+        _ffi.call("tsdf_hash_get_mesh", self._h, _ffi.ptr(v), _ffi.ptr(n), _ffi.ptr(c), _ffi.ptr(f))
+        if not keys:
+            return v, n, c, f
+        k = np.empty(nv.value, np.int64)
+        _ffi.call("tsdf_hash_get_mesh_keys", self._h, _ffi.ptr(k))
+        return v, n, c, f, k
+
+    def mesh_info(self) -> dict:
+        """The last extract_mesh: live_blocks, mesh_blocks (block coordinates meshed), scratch_bytes
+        (every device allocation it made, the mesh included), n_verts, n_tris."""
+        s = _ffi.HashMeshInfo()
+        _ffi.call("tsdf_hash_mesh_info", self._h, ctypes.byref(s))
+        return s.as_dict()
+
     def get_mesh(self):
-        """hash_fusion.py:465-484: marching cubes of the densified volume, on the device."""
-        return self._as_grid().get_mesh()
+        """hash_fusion.py:465-484: (verts, faces, norms, colors), marching cubes of the table's
+        blocks on the device (the mesh of the densified volume, without densifying)."""
+        v, n, c, f = self.extract_mesh()
+        return v, f, n, c
 
     def get_point_cloud(self):
-        """hash_fusion.py:486-507."""
-        return self._as_grid().get_point_cloud()
+        """hash_fusion.py:486-507: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""
+        v, _, c, _ = self.extract_mesh(normals=False, faces=False)
+        return np.hstack([v, c])
 
     # ------------------------------------------------------------------ misc
     def sync(self):
