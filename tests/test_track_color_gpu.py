@@ -3,7 +3,8 @@ DESIGN.md §7f) against its NumPy restatement (tests/icp_color_ref.py on top of 
 both code maps and both residual maps byte-identical, all 56 sums within what the order of addition
 can change, the geometric half byte-identical to tsdf_icp_linearize, every pose update reproduced
 step by step, and the final poses within the bounds tests/test_track_color_cpu.py measured -- on a
-single plane, where the geometric track alone is lost.  Volumes <= 128^3, images <= 83 x 61."""
+single plane, where the geometric track alone is lost.  Volumes <= 128^3, images <= 83 x 61 but
+for one frame of 131 x 97."""
 import ctypes
 
 import numpy as np
@@ -120,6 +121,41 @@ def test_linearize_rgbd_equals_the_restatement(tr, plane_maps, lin_refs, name, k
     assert old["code"].tobytes() == got["code"].tobytes() and old["residual"].tobytes() == got["residual"].tobytes()
     assert (old["inliers"], old["candidates"]) == (got["inliers"], got["candidates"])
     assert np.array_equal(got["color_A"], got["color_A"].T) and np.array_equal(got["color_b"], got["color_sums"][21:27])
+
+
+def test_linearize_131x97_second_trip_of_the_finish(tr, plane_maps):
+    """The other frames of the suite give at most 20 partial records, so the finish's lanes add one
+    record each.  The plane's analytic frame through a 131x97 frame camera (FRAME_K scaled; the model
+    maps are the 83x61 ones) gives 50: slices 0..17 add two records, slices 18..31 one.  Both entry
+    points, u16, stride 1: codes and residuals byte-identical to the restatement, counts equal, sums
+    within N 2^-52 sum|term|."""
+    hw = (97, 131)
+    K = I.FRAME_K.copy()
+    K[0] *= hw[1] / I.FRAME_HW[1]
+    K[1] *= hw[0] / I.FRAME_HW[0]
+    frame, rgb = C.plane_render(K=K, hw=hw, extras=True)
+    assert -(-frame.size // 256) == 50  # one partial record per workgroup of 256 pixels
+    d, n, c = plane_maps["model"]
+    M = I.offset_2cm_1deg()
+    geo = I.linearize(frame, K, M, d, n, I.MODEL_K, np.eye(4))
+    col = C.linearize_color(frame, rgb, K, M, d, c, I.MODEL_K)
+    assert geo["inliers"] >= 20 and col["inliers"] >= 20  # (about 10^4 each: the bound below is not vacuous)
+    old = tr.icp_linearize(frame, K, M, d, n, I.MODEL_K, np.eye(4))
+    got = tr.icp_linearize_rgbd(frame, rgb, K, M, d, n, c, I.MODEL_K, np.eye(4))
+    for res in (old, got):
+        assert res["code"].tobytes() == geo["code"].tobytes()
+        assert res["residual"].tobytes() == geo["resid"].tobytes()
+        assert (res["inliers"], res["candidates"]) == (geo["inliers"], geo["candidates"])
+    assert got["color_code"].tobytes() == col["code"].tobytes()
+    assert got["color_residual"].tobytes() == col["resid"].tobytes()
+    assert (got["color_inliers"], got["color_candidates"]) == (col["inliers"], col["candidates"])
+    for name, sums, ref in (("icp_linearize", old["sums"], geo), ("rgbd geometry", got["sums"], geo),
+                            ("rgbd colour", got["color_sums"], col)):
+        bound = ref["inliers"] * 2.0 ** -52 * ref["abs_sums"]
+        err = np.abs(sums - ref["sums"])
+        print(f"131x97 {name}: inliers {ref['inliers']}, max |sum - fsum| / bound {np.max(err / bound):.3f}")
+        assert (err <= bound).all()
+    assert old["sums"].tobytes() == got["sums"].tobytes()
 
 
 def test_optional_maps_and_invalid_65535(tr, plane_maps, lin_refs):

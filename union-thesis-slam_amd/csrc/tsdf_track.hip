@@ -1,9 +1,10 @@
-// tsdf_track.hip -- camera tracking against the fused model (DESIGN.md §7e): frame-to-model
-// point-to-plane ICP, single resolution, geometry only.  Not in the reference (its poses come from
-// files).  A depth frame is aligned against the depth and normal maps of a raycast (§7d): per
-// sampled pixel a projective association and one row of the linearised point-to-plane system, a
-// deterministic reduction to the 6x6 normal equations, and the Cholesky solve and pose update on
-// the device, so that an N-iteration alignment costs one host synchronisation.
+// tsdf_track.hip -- camera tracking against the fused model (DESIGN.md §7e, §7f): frame-to-model
+// point-to-plane ICP, single resolution, with an optional photometric term.  Not in the reference
+// (its poses come from files).  A depth frame is aligned against the depth and normal maps of a
+// raycast (§7d): per sampled pixel a projective association and one row of the linearised
+// point-to-plane system, a deterministic reduction to the 6x6 normal equations, and the Cholesky
+// solve and pose update on the device, so that an N-iteration alignment costs one host
+// synchronisation.
 //
 // The contract (restated in NumPy by tests/icp_ref.py; codes and residuals matched bit for bit):
 // everything per pixel is a separately rounded f32 operation in the model camera's frame, the sums
@@ -12,18 +13,17 @@
 //   2 behind the model camera or outside its image     3 no model surface there
 //   4 too far (dist_max)    5 normals disagree (cos_min)    6 inlier
 //
-// Two kernels per iteration.  k_icp_linearize: one lane per sampled pixel over a grid-stride loop,
-// 28 f64 sums and 2 counts per lane, a butterfly over the wave, the waves of a workgroup through
-// LDS in wave order, one partial record per workgroup.  k_icp_finish (one workgroup of 1024): the partial
-// records in a fixed order, then one lane solves and updates.  No floating-point atomics anywhere:
-// the order of every addition is fixed by the launch shape, which depends on the image size, the
-// stride and the device only.  The finish is a kernel of its own, not the last workgroup of the
-// linearise: a kernel boundary makes the partial records visible across the XCDs' L2s by itself,
-// where a last-arriver protocol needs an agent-scope release per workgroup, a ticket atomic and an
-// acquire, for the price of one more launch of a few microseconds (§7e).
-//
-// With the frame's RGB image a photometric term joins the geometric one (§7f): k_icp_photo_prep,
-// k_icp_linearize_rgbd and k_icp_finish_rgbd below, behind entry points of their own.
+// Two kernels per iteration, each a template over COLOR: false is the geometric track, true adds
+// the photometric term of §7f (see the banner above k_icp_linearize).  k_icp_linearize: one lane per
+// sampled pixel over a grid-stride loop, 28 f64 sums and 2 counts per lane and term, a butterfly
+// over the wave, the waves of a workgroup through LDS in wave order, one partial record per
+// workgroup.  k_icp_finish (one workgroup of 1024): the partial records in a fixed order, then one
+// lane solves and updates.  No floating-point atomics anywhere: the order of every addition is fixed
+// by the launch shape, which depends on the image size, the stride and the device only.  The finish
+// is a kernel of its own, not the last workgroup of the linearise: a kernel boundary makes the
+// partial records visible across the XCDs' L2s by itself, where a last-arriver protocol needs an
+// agent-scope release per workgroup, a ticket atomic and an acquire, for the price of one more
+// launch of a few microseconds (§7e).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,7 +36,7 @@ using namespace tsdf;
 namespace tsdf {
 
 constexpr int kIcpWG = 256;
-constexpr int kIcpRec = 32;       // doubles per partial record: 28 sums, inliers, candidates, 2 unused
+constexpr int kIcpRec = 32;       // doubles per term of a partial record: 28 sums, inliers, candidates, 2 unused
 constexpr int kIcpMaxIter = TSDF_ICP_MAX_ITER;
 constexpr int kIcpRunning = 0;    // internal status while iterating (the public ones: TSDF_TRACK_*)
 
@@ -55,6 +55,9 @@ struct IcpRecord {
     double w_norm, t_norm;
     int status;          // after the iteration
     int pad;
+    // the colour term's (§7f): written by the RGB-D finish and read after an RGB-D call only
+    double csums[28];    // the same layout (not scaled by lambda^2)
+    long long c_inliers, c_candidates;
 };
 
 // Device buffers of a handle's tracks, or of a device's handle-less linearisations: grown on
@@ -105,9 +108,15 @@ struct IcpArgs {
     float fxm, fym, cxm, cym;
     float dist_max, cos_min;
     const IcpState* st;
-    double* partial;     // gridDim.x records of kIcpRec doubles
+    double* partial;     // gridDim.x records of kIcpRec doubles (twice that with the colour term)
     unsigned char* code;
     float* resid;
+    // the colour term (§7f); null / 0 for the geometric instance, which fi == nullptr selects
+    const unsigned char* fi;  // Hf x Wf: the frame's intensity
+    const float4* tex;        // Hm x Wm: (I, Gx, Gy, D) of the model, all 0 where invalid
+    float color_max;
+    unsigned char* ccode;
+    float* cresid;
 };
 
 // x_u = f32((u - cx) / fx), y_v = f32((v - cy) / fy): f64, one rounding (§7d step 1)
@@ -141,280 +150,11 @@ __device__ inline float depth_at(const IcpArgs& a, int u, int v) {
 
 __device__ inline bool good_depth(float d) { return d > 0.0f && d < INFINITY; }
 
-template <int DK>
-__global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
-    if (a.st->status != kIcpRunning) return;  // a status is set: the queued launches fall through
-    float M[12];
-    for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
-    const float dist2 = a.dist_max * a.dist_max;
-
-    double s[28];
-#pragma unroll
-    for (int i = 0; i < 28; ++i) s[i] = 0.0;
-    unsigned n_in = 0, n_cand = 0;
-
-    const long long n = (long long)a.su * a.sv;
-    for (long long i = (long long)blockIdx.x * kIcpWG + threadIdx.x; i < n; i += (long long)gridDim.x * kIcpWG) {
-        const int u = (int)(i % a.su) * a.stride, v = (int)(i / a.su) * a.stride;
-        int code = 0;
-        float r = 0.0f, J[6];
-        do {
-            if (u >= a.Wf - 1 || v >= a.Hf - 1) break;
-            const float d = depth_at<DK>(a, u, v);
-            if (!good_depth(d)) break;
-            code = 1;
-            const float dr = depth_at<DK>(a, u + 1, v), dd = depth_at<DK>(a, u, v + 1);
-            if (!good_depth(dr) || !good_depth(dd)) break;
-            const float xu = a.xf[u], xr = a.xf[u + 1], yv = a.yf[v], yd = a.yf[v + 1];
-            const float V[3] = {xu * d, yv * d, d};
-            const float A[3] = {xr * dr - V[0], yv * dr - V[1], dr - V[2]};
-            const float B[3] = {xu * dd - V[0], yd * dd - V[1], dd - V[2]};
-            const float c[3] = {B[1] * A[2] - B[2] * A[1], B[2] * A[0] - B[0] * A[2], B[0] * A[1] - B[1] * A[0]};
-            const float l = __fsqrt_rn((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
-            if (l == 0.0f) break;
-            const float nf[3] = {c[0] / l, c[1] / l, c[2] / l};
-            float p[3], m[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                p[k] = ((M[4 * k] * V[0] + M[4 * k + 1] * V[1]) + M[4 * k + 2] * V[2]) + M[4 * k + 3];
-                m[k] = (M[4 * k] * nf[0] + M[4 * k + 1] * nf[1]) + M[4 * k + 2] * nf[2];
-            }
-            code = 2;
-            if (p[2] <= 0.0f) break;
-            const float uf = rintf(a.fxm * (p[0] / p[2]) + a.cxm), vf = rintf(a.fym * (p[1] / p[2]) + a.cym);
-            if (!(uf >= 0.0f && uf <= (float)(a.Wm - 1) && vf >= 0.0f && vf <= (float)(a.Hm - 1))) break;
-            const int um = (int)uf, vm = (int)vf;
-            const size_t pm = (size_t)vm * a.Wm + um;
-            const float dm = a.dm[pm];
-            const float nw[3] = {a.nm[3 * pm], a.nm[3 * pm + 1], a.nm[3 * pm + 2]};
-            code = 3;
-            if (!(dm > 0.0f) || (nw[0] == 0.0f && nw[1] == 0.0f && nw[2] == 0.0f)) break;
-            const float q[3] = {a.xm[um] * dm, a.ym[vm] * dm, dm};
-            float nn[3], e[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                nn[k] = (a.Rm[k] * nw[0] + a.Rm[3 + k] * nw[1]) + a.Rm[6 + k] * nw[2];
-                e[k] = q[k] - p[k];
-            }
-            code = 4;
-            if ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2] > dist2) break;
-            code = 5;
-            if ((nn[0] * m[0] + nn[1] * m[1]) + nn[2] * m[2] < a.cos_min) break;
-            code = 6;
-            r = (nn[0] * e[0] + nn[1] * e[1]) + nn[2] * e[2];
-            J[0] = p[1] * nn[2] - p[2] * nn[1];
-            J[1] = p[2] * nn[0] - p[0] * nn[2];
-            J[2] = p[0] * nn[1] - p[1] * nn[0];
-            J[3] = nn[0];
-            J[4] = nn[1];
-            J[5] = nn[2];
-        } while (false);
-        if (code >= 2) ++n_cand;
-        if (code == 6) {
-            ++n_in;
-            int k = 0;
-#pragma unroll
-            for (int x = 0; x < 6; ++x)
-#pragma unroll
-                for (int y = x; y < 6; ++y) s[k++] += (double)J[x] * (double)J[y];
-#pragma unroll
-            for (int x = 0; x < 6; ++x) s[21 + x] += (double)J[x] * (double)r;
-            s[27] += (double)r * (double)r;
-        }
-        const size_t pf = (size_t)v * a.Wf + u;
-        if (a.code) a.code[pf] = (unsigned char)code;
-        if (a.resid) a.resid[pf] = r;
-    }
-
-    // the wave: a butterfly (every lane ends with the same sum, formed in the same order)
-#pragma unroll
-    for (int i = 0; i < 28; ++i)
-        for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
-    for (int o = 32; o > 0; o >>= 1) {
-        n_in += __shfl_xor(n_in, o);
-        n_cand += __shfl_xor(n_cand, o);
-    }
-    // the workgroup: through LDS, waves added in wave order
-    __shared__ double sh[kIcpWG / 64][kIcpRec];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 28; ++i) sh[wave][i] = s[i];
-        sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
-        sh[wave][29] = (double)n_cand;
-    }
-    __syncthreads();
-    if (threadIdx.x < 30) {
-        double t = sh[0][threadIdx.x];
-        for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
-        a.partial[(size_t)blockIdx.x * kIcpRec + threadIdx.x] = t;
-    }
-}
-
-struct FinishArgs {
-    const double* partial;
-    int n_partial;
-    IcpState* st;
-    IcpRecord* rec;   // this iteration's
-    int solve;        // 0: sums only (tsdf_icp_linearize)
-    int last;         // the last iteration of the call: still running afterwards means max_iter
-    long long min_inliers;
-    double eps_rot, eps_trans;
-};
-
-constexpr int kFinSlices = 32;
-constexpr int kFinWG = kFinSlices * kIcpRec;  // 1024: the loads of the partial records spread over many lanes
-
-__global__ __launch_bounds__(kFinWG) void k_icp_finish(FinishArgs a) {
-    if (a.st->status != kIcpRunning) return;
-    // the partial records: column j by slice (records slice, slice + 32, ...), then the slices in order
-    __shared__ double sh[kFinSlices][kIcpRec];
-    __shared__ double tot[kIcpRec];
-    const int j = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    double t = 0.0;
-    if (j < 30) {
-#pragma unroll 4
-        for (int g = slice; g < a.n_partial; g += kFinSlices) t += a.partial[(size_t)g * kIcpRec + j];
-    }
-    sh[slice][j] = t;
-    __syncthreads();
-    if (threadIdx.x < 30) {
-        double x = sh[0][threadIdx.x];
-        for (int k = 1; k < kFinSlices; ++k) x += sh[k][threadIdx.x];
-        tot[threadIdx.x] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-
-    IcpRecord& R = *a.rec;
-    for (int i = 0; i < 28; ++i) R.sums[i] = tot[i];
-    R.inliers = (long long)tot[28];
-    R.candidates = (long long)tot[29];
-    R.w_norm = R.t_norm = 0.0;
-    double M[16];
-    for (int i = 0; i < 16; ++i) M[i] = a.st->M[i];
-    int status = kIcpRunning;
-    if (a.solve) {
-        // A = L L^T (lower triangle, in place), then the two triangular solves
-        double L[6][6], b[6];
-        int k = 0;
-        for (int x = 0; x < 6; ++x)
-            for (int y = x; y < 6; ++y) L[y][x] = tot[k++];
-        for (int x = 0; x < 6; ++x) b[x] = tot[21 + x];
-        bool ok = R.inliers >= a.min_inliers;
-        for (int c = 0; c < 6 && ok; ++c) {
-            double d = L[c][c];
-            for (int e = 0; e < c; ++e) d -= L[c][e] * L[c][e];
-            if (!(d > 0.0) || !(d < INFINITY)) {
-                ok = false;
-                break;
-            }
-            d = sqrt(d);
-            L[c][c] = d;
-            for (int r = c + 1; r < 6; ++r) {
-                double x = L[r][c];
-                for (int e = 0; e < c; ++e) x -= L[r][e] * L[c][e];
-                L[r][c] = x / d;
-            }
-        }
-        if (!ok) {
-            status = TSDF_TRACK_LOST;
-        } else {
-            double y[6], xi[6];
-            for (int r = 0; r < 6; ++r) {
-                double x = b[r];
-                for (int e = 0; e < r; ++e) x -= L[r][e] * y[e];
-                y[r] = x / L[r][r];
-            }
-            for (int r = 5; r >= 0; --r) {
-                double x = y[r];
-                for (int e = r + 1; e < 6; ++e) x -= L[e][r] * xi[e];
-                xi[r] = x / L[r][r];
-            }
-            // E = Rodrigues(w) with translation t; M <- E M
-            const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
-            const double th2 = (w0 * w0 + w1 * w1) + w2 * w2, th = sqrt(th2);
-            double A = 1.0, Bc = 0.5;
-            if (th > 1e-8) {
-                A = sin(th) / th;
-                Bc = (1.0 - cos(th)) / th2;
-            }
-            const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-            double E[9];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) {
-                    const double k2 = (K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c]) + K[3 * r + 2] * K[6 + c];
-                    E[3 * r + c] = ((r == c ? 1.0 : 0.0) + A * K[3 * r + c]) + Bc * k2;
-                }
-            double N[16];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    double x = (E[3 * r] * M[c] + E[3 * r + 1] * M[4 + c]) + E[3 * r + 2] * M[8 + c];
-                    if (c == 3) x += xi[3 + r];
-                    N[4 * r + c] = x;
-                }
-            N[12] = N[13] = N[14] = 0.0;
-            N[15] = 1.0;
-            bool finite = true;
-            for (int i = 0; i < 12; ++i) finite = finite && N[i] - N[i] == 0.0;
-            if (!finite) {
-                status = TSDF_TRACK_LOST;
-            } else {
-                for (int i = 0; i < 16; ++i) M[i] = N[i];
-                R.w_norm = th;
-                R.t_norm = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
-                if (R.w_norm <= a.eps_rot && R.t_norm <= a.eps_trans) status = TSDF_TRACK_CONVERGED;
-                else if (a.last) status = TSDF_TRACK_MAX_ITER;
-            }
-        }
-    }
-    for (int i = 0; i < 16; ++i) {
-        R.M[i] = M[i];
-        a.st->M[i] = M[i];
-    }
-    R.status = status;
-    a.st->iters += 1;
-    a.st->status = status;
-}
-
-// ---- the photometric term ----------------------------------------------------------
-// k_icp_linearize_rgbd does the work of k_icp_linearize (the same operations in the same order: the
-// same bytes) and, in the same pass over the frame, the colour term: the frame's depth is read once
-// and p is shared.  Colour codes:
-//   0 not sampled / no depth     1 behind the model camera or footprint outside its image
-//   2 an invalid texel under the footprint     3 occluded (dist_max)     4 too different (color_max_diff)
-//   5 inlier
-// The partial record doubles: columns 0..31 as k_icp_linearize's, 32..59 the colour sums, 60 / 61 the
-// colour inliers / candidates.  k_icp_finish_rgbd adds each half in k_icp_finish's order, combines
-// them with lambda^2 and solves.  The two geometry-only kernels above are left as they were; what
-// they do is repeated here, not shared, so that their code does not change.
-constexpr int kRgbdRec = 2 * kIcpRec;  // doubles per partial record
-
-struct IcpRecordRgbd {
-    double M[16];
-    double sums[28];     // geometric, as IcpRecord's
-    long long inliers, candidates;
-    double w_norm, t_norm;
-    int status;
-    int pad;
-    double csums[28];    // colour, the same layout (not scaled by lambda^2)
-    long long c_inliers, c_candidates;
-};
-
-struct RgbdArgs {
-    IcpArgs g;
-    const unsigned char* fi;  // Hf x Wf: the frame's intensity
-    const float4* tex;        // Hm x Wm: (I, Gx, Gy, D) of the model, all 0 where invalid
-    float color_max;
-    unsigned char* ccode;
-    float* cresid;
-};
-
 __device__ inline float intensity_u8(const unsigned char* c) {
     return (float)((77u * c[0] + 150u * c[1] + 29u * c[2]) >> 8);
 }
 
-// Once per call: the frame's intensity image and the model's photo texels.
+// Once per RGB-D call: the frame's intensity image and the model's photo texels.
 __global__ void k_icp_photo_prep(const unsigned char* rgb, int n_frame, unsigned char* fi, const unsigned char* mc,
                                  const float* dm, int Hm, int Wm, float4* tex) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -440,25 +180,40 @@ __device__ inline float bilerp(float t00, float t01, float t10, float t11, float
     return lerpf(lerpf(t00, t01, tx), lerpf(t10, t11, tx), ty);
 }
 
-template <int DK>
-__global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
-    const IcpArgs& a = A.g;
-    if (a.st->status != kIcpRunning) return;
+// ---- the iteration's two kernels ----------------------------------------------
+// COLOR = false is the geometric track.  COLOR = true adds, in the same pass over the frame, the
+// photometric term: the frame's depth is read once, p and the projection are shared, and the
+// geometric half is the same operations in the same order (the same bytes).  What COLOR switches, at
+// compile time: the colour half of the pixel loop, its 28 sums and 2 counts, the second half of the
+// partial record (columns 32..59 the colour sums, 60 / 61 the colour inliers / candidates), and in
+// the finish the second column per lane, the lambda^2 combination and the record's tail.  Colour
+// codes:
+//   0 not sampled / no depth     1 behind the model camera or footprint outside its image
+//   2 an invalid texel under the footprint     3 occluded (dist_max)     4 too different (color_max_diff)
+//   5 inlier
+template <int DK, bool COLOR>
+__global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
+    constexpr int kSums = COLOR ? 56 : 28;               // per lane: 0..27 geometric, 28..55 colour
+    constexpr int kRec = COLOR ? 2 * kIcpRec : kIcpRec;  // doubles per partial record
+    if (a.st->status != kIcpRunning) return;  // a status is set: the queued launches fall through
     float M[12];
     for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
     const float dist2 = a.dist_max * a.dist_max;
 
-    double s[56];  // 0..27 geometric, 28..55 colour
+    double s[kSums];
 #pragma unroll
-    for (int i = 0; i < 56; ++i) s[i] = 0.0;
-    unsigned n_in = 0, n_cand = 0, c_in = 0, c_cand = 0;
+    for (int i = 0; i < kSums; ++i) s[i] = 0.0;
+    unsigned n_in = 0, n_cand = 0;
+    [[maybe_unused]] unsigned c_in = 0, c_cand = 0;
 
     const long long n = (long long)a.su * a.sv;
     for (long long i = (long long)blockIdx.x * kIcpWG + threadIdx.x; i < n; i += (long long)gridDim.x * kIcpWG) {
         const int u = (int)(i % a.su) * a.stride, v = (int)(i / a.su) * a.stride;
         const size_t pf = (size_t)v * a.Wf + u;
-        int code = 0, cc = 0;
-        float r = 0.0f, J[6], rc = 0.0f, Jc[6];
+        int code = 0;
+        float r = 0.0f, J[6];
+        [[maybe_unused]] int cc = 0;
+        [[maybe_unused]] float rc = 0.0f, Jc[6];
         const float d = depth_at<DK>(a, u, v);
         if (good_depth(d)) {
             const float xu = a.xf[u], yv = a.yf[v];
@@ -468,7 +223,7 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
             for (int k = 0; k < 3; ++k) p[k] = ((M[4 * k] * V[0] + M[4 * k + 1] * V[1]) + M[4 * k + 2] * V[2]) + M[4 * k + 3];
             // the projection both halves start from (the geometric half rounds it, the colour half floors it)
             const float x = a.fxm * (p[0] / p[2]) + a.cxm, y = a.fym * (p[1] / p[2]) + a.cym;
-            // the geometric half: k_icp_linearize's operations
+            // the geometric half
             do {
                 if (u >= a.Wf - 1 || v >= a.Hf - 1) break;
                 code = 1;
@@ -515,13 +270,13 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
                 J[5] = nn[2];
             } while (false);
             // the colour half
-            do {
+            if constexpr (COLOR) do {
                 cc = 1;
                 if (p[2] <= 0.0f) break;
                 const float x0 = floorf(x), y0 = floorf(y);
                 if (!(x0 >= 1.0f && x0 <= (float)(a.Wm - 3) && y0 >= 1.0f && y0 <= (float)(a.Hm - 3))) break;
                 const size_t pm = (size_t)(int)y0 * a.Wm + (int)x0;  // rows y0, y0 + 1 <= Hm - 2; columns x0, x0 + 1 <= Wm - 2
-                const float4 t00 = A.tex[pm], t01 = A.tex[pm + 1], t10 = A.tex[pm + a.Wm], t11 = A.tex[pm + a.Wm + 1];
+                const float4 t00 = a.tex[pm], t01 = a.tex[pm + 1], t10 = a.tex[pm + a.Wm], t11 = a.tex[pm + a.Wm + 1];
                 cc = 2;
                 if (!(t00.w > 0.0f && t01.w > 0.0f && t10.w > 0.0f && t11.w > 0.0f)) break;
                 const float tx = x - x0, ty = y - y0;
@@ -529,9 +284,9 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
                 cc = 3;
                 if (fabsf(Db - p[2]) > a.dist_max) break;
                 const float Ib = bilerp(t00.x, t01.x, t10.x, t11.x, tx, ty);
-                const float res = (float)A.fi[pf] - Ib;
+                const float res = (float)a.fi[pf] - Ib;
                 cc = 4;
-                if (fabsf(res) > A.color_max) break;
+                if (fabsf(res) > a.color_max) break;
                 cc = 5;
                 rc = res;
                 const float ga = bilerp(t00.y, t01.y, t10.y, t11.y, tx, ty) * a.fxm;
@@ -559,71 +314,82 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize_rgbd(RgbdArgs A) {
             for (int x = 0; x < 6; ++x) s[21 + x] += (double)J[x] * (double)r;
             s[27] += (double)r * (double)r;
         }
-        if (cc >= 2) ++c_cand;
-        if (cc == 5) {
-            ++c_in;
-            int k = 28;
-#pragma unroll
-            for (int x = 0; x < 6; ++x)
-#pragma unroll
-                for (int y = x; y < 6; ++y) s[k++] += (double)Jc[x] * (double)Jc[y];
-#pragma unroll
-            for (int x = 0; x < 6; ++x) s[49 + x] += (double)Jc[x] * (double)rc;
-            s[55] += (double)rc * (double)rc;
-        }
         if (a.code) a.code[pf] = (unsigned char)code;
         if (a.resid) a.resid[pf] = r;
-        if (A.ccode) A.ccode[pf] = (unsigned char)cc;
-        if (A.cresid) A.cresid[pf] = rc;
+        if constexpr (COLOR) {
+            if (cc >= 2) ++c_cand;
+            if (cc == 5) {
+                ++c_in;
+                int k = 28;
+#pragma unroll
+                for (int x = 0; x < 6; ++x)
+#pragma unroll
+                    for (int y = x; y < 6; ++y) s[k++] += (double)Jc[x] * (double)Jc[y];
+#pragma unroll
+                for (int x = 0; x < 6; ++x) s[49 + x] += (double)Jc[x] * (double)rc;
+                s[55] += (double)rc * (double)rc;
+            }
+            if (a.ccode) a.ccode[pf] = (unsigned char)cc;
+            if (a.cresid) a.cresid[pf] = rc;
+        }
     }
 
-    // the wave's butterfly, then the waves in wave order through LDS: as k_icp_linearize
+    // the wave: a butterfly (every lane ends with the same sum, formed in the same order)
 #pragma unroll
-    for (int i = 0; i < 56; ++i)
+    for (int i = 0; i < kSums; ++i)
         for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
     for (int o = 32; o > 0; o >>= 1) {
         n_in += __shfl_xor(n_in, o);
         n_cand += __shfl_xor(n_cand, o);
-        c_in += __shfl_xor(c_in, o);
-        c_cand += __shfl_xor(c_cand, o);
+        if constexpr (COLOR) {
+            c_in += __shfl_xor(c_in, o);
+            c_cand += __shfl_xor(c_cand, o);
+        }
     }
-    __shared__ double sh[kIcpWG / 64][kRgbdRec];
+    // the workgroup: through LDS, waves added in wave order
+    __shared__ double sh[kIcpWG / 64][kRec];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < 28; ++i) {
-            sh[wave][i] = s[i];
-            sh[wave][kIcpRec + i] = s[28 + i];
-        }
+        for (int i = 0; i < 28; ++i) sh[wave][i] = s[i];
         sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
         sh[wave][29] = (double)n_cand;
-        sh[wave][kIcpRec + 28] = (double)c_in;
-        sh[wave][kIcpRec + 29] = (double)c_cand;
-        sh[wave][30] = sh[wave][31] = sh[wave][kIcpRec + 30] = sh[wave][kIcpRec + 31] = 0.0;
+        sh[wave][30] = sh[wave][31] = 0.0;
+        if constexpr (COLOR) {
+#pragma unroll
+            for (int i = 0; i < 28; ++i) sh[wave][kIcpRec + i] = s[28 + i];
+            sh[wave][kIcpRec + 28] = (double)c_in;
+            sh[wave][kIcpRec + 29] = (double)c_cand;
+            sh[wave][kIcpRec + 30] = sh[wave][kIcpRec + 31] = 0.0;
+        }
     }
     __syncthreads();
-    if (threadIdx.x < kRgbdRec) {
+    if (threadIdx.x < kRec) {
         double t = sh[0][threadIdx.x];
         for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
-        a.partial[(size_t)blockIdx.x * kRgbdRec + threadIdx.x] = t;
+        a.partial[(size_t)blockIdx.x * kRec + threadIdx.x] = t;
     }
 }
 
-struct FinishRgbdArgs {
-    const double* partial;  // n_partial records of kRgbdRec doubles
+struct FinishArgs {
+    const double* partial;  // n_partial records, as wide as the linearise instance wrote them
     int n_partial;
     IcpState* st;
-    IcpRecordRgbd* rec;
-    int solve, last;
+    IcpRecord* rec;   // this iteration's
+    int solve;        // 0: sums only (the handle-less linearisations)
+    int last;         // the last iteration of the call: still running afterwards means max_iter
     long long min_inliers;
     double eps_rot, eps_trans;
-    double l2;              // color_weight^2
+    double l2;        // color_weight^2 (the RGB-D instance)
 };
 
-// A xi = b by Cholesky, E = Rodrigues(w) with translation t, M <- E M: k_icp_finish's arithmetic on
-// the 27 sums in t.  Returns the status; M, w_norm and t_norm change only when the step is taken.
-// Every loop is unrolled so that L, y and xi are never indexed by a variable: they stay in registers
-// (no private segment), where k_icp_finish keeps 304 bytes of it.
+constexpr int kFinSlices = 32;
+constexpr int kFinWG = kFinSlices * kIcpRec;  // 1024: the loads of the partial records spread over many lanes
+
+// A xi = b by Cholesky (A = L L^T, lower triangle, then the two triangular solves), E = Rodrigues(w)
+// with translation t, M <- E M, on the 27 sums in t.  Returns the status; M, w_norm and t_norm change
+// only when the step is taken.  Every loop is unrolled so that L, y and xi are never indexed by a
+// variable: they stay in registers (no private segment).
 __device__ int icp_solve_update(const double* t, bool enough, int last, double eps_rot, double eps_trans, double* M,
                                 double* w_norm, double* t_norm) {
     double L[6][6], b[6];
@@ -709,25 +475,29 @@ __device__ int icp_solve_update(const double* t, bool enough, int last, double e
     return last ? TSDF_TRACK_MAX_ITER : kIcpRunning;
 }
 
-__global__ __launch_bounds__(kFinWG) void k_icp_finish_rgbd(FinishRgbdArgs a) {
+template <bool COLOR>
+__global__ __launch_bounds__(kFinWG) void k_icp_finish(FinishArgs a) {
+    constexpr int kHalves = COLOR ? 2 : 1, kRec = kHalves * kIcpRec;
     if (a.st->status != kIcpRunning) return;
-    // lane (slice, j) adds column j of both halves over the records slice, slice + 32, ...; then the
-    // slices in order: each half in exactly k_icp_finish's order of addition
-    __shared__ double sh[kFinSlices][kRgbdRec];
-    __shared__ double tot[kRgbdRec];
+    // the partial records: lane (slice, j) adds column j of each half over the records slice,
+    // slice + 32, ...; then the slices in order.  A half is added in the same order in both instances
+    // (which is what makes lambda = 0 byte-identical to the geometric track)
+    __shared__ double sh[kFinSlices][kRec];
+    __shared__ double tot[kRec];
     const int j = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    double tg = 0.0, tc = 0.0;
+    double t[kHalves];
+#pragma unroll
+    for (int h = 0; h < kHalves; ++h) t[h] = 0.0;
     if (j < 30) {
 #pragma unroll 4
-        for (int g = slice; g < a.n_partial; g += kFinSlices) {
-            tg += a.partial[(size_t)g * kRgbdRec + j];
-            tc += a.partial[(size_t)g * kRgbdRec + kIcpRec + j];
-        }
+        for (int g = slice; g < a.n_partial; g += kFinSlices)
+#pragma unroll
+            for (int h = 0; h < kHalves; ++h) t[h] += a.partial[(size_t)g * kRec + h * kIcpRec + j];
     }
-    sh[slice][j] = tg;
-    sh[slice][kIcpRec + j] = tc;
+#pragma unroll
+    for (int h = 0; h < kHalves; ++h) sh[slice][h * kIcpRec + j] = t[h];
     __syncthreads();
-    if (threadIdx.x < kRgbdRec) {
+    if (threadIdx.x < kRec) {
         double x = sh[0][threadIdx.x];
         for (int k = 1; k < kFinSlices; ++k) x += sh[k][threadIdx.x];
         tot[threadIdx.x] = x;
@@ -735,23 +505,25 @@ __global__ __launch_bounds__(kFinWG) void k_icp_finish_rgbd(FinishRgbdArgs a) {
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    IcpRecordRgbd& R = *a.rec;
-    for (int i = 0; i < 28; ++i) {
-        R.sums[i] = tot[i];
-        R.csums[i] = tot[kIcpRec + i];
-    }
+    IcpRecord& R = *a.rec;
+    for (int i = 0; i < 28; ++i) R.sums[i] = tot[i];
     R.inliers = (long long)tot[28];
     R.candidates = (long long)tot[29];
-    R.c_inliers = (long long)tot[kIcpRec + 28];
-    R.c_candidates = (long long)tot[kIcpRec + 29];
+    if constexpr (COLOR) {
+        for (int i = 0; i < 28; ++i) R.csums[i] = tot[kIcpRec + i];
+        R.c_inliers = (long long)tot[kIcpRec + 28];
+        R.c_candidates = (long long)tot[kIcpRec + 29];
+    }
     R.w_norm = R.t_norm = 0.0;
     double M[16];
     for (int i = 0; i < 16; ++i) M[i] = a.st->M[i];
     int status = kIcpRunning;
     if (a.solve) {
-        double t[27];  // A = A_g + lambda^2 A_c, b = b_g + lambda^2 b_c
-        for (int i = 0; i < 27; ++i) t[i] = tot[i] + a.l2 * tot[kIcpRec + i];
-        status = icp_solve_update(t, R.inliers >= a.min_inliers, a.last, a.eps_rot, a.eps_trans, M, &R.w_norm, &R.t_norm);
+        double comb[27];  // A = A_g + lambda^2 A_c, b = b_g + lambda^2 b_c; the geometric totals go in as they are
+        if constexpr (COLOR)
+            for (int i = 0; i < 27; ++i) comb[i] = tot[i] + a.l2 * tot[kIcpRec + i];
+        status = icp_solve_update(COLOR ? comb : tot, R.inliers >= a.min_inliers, a.last, a.eps_rot, a.eps_trans, M, &R.w_norm,
+                                  &R.t_norm);
     }
     for (int i = 0; i < 16; ++i) {
         R.M[i] = M[i];
@@ -795,9 +567,29 @@ int check_params(const tsdf_icp_params_t* p) {
     return TSDF_OK;
 }
 
+int check_color_params(const tsdf_icp_color_params_t* q) {
+    if (!q) return set_error(TSDF_E_ARG, "null color params pointer");
+    if (!(q->color_weight >= 0.0) || !std::isfinite(q->color_weight))
+        return set_error(TSDF_E_ARG, "color_weight must be finite and >= 0 (got %g)", q->color_weight);
+    if (!(q->color_max_diff > 0.0f)) return set_error(TSDF_E_ARG, "color_max_diff must be > 0 (got %g)", (double)q->color_max_diff);
+    return TSDF_OK;
+}
+
 struct Cameras {
     int Hf, Wf, Hm, Wm;
     const double *Kf, *Km, *model_pose;
+};
+
+// The device images of one call.  rgb and mc (the frame's RGB8 image and the model's colour map) are
+// null for a geometric call; the four maps are optional outputs.
+struct Images {
+    const void* depth;
+    const float *dm, *nm;
+    const unsigned char *rgb, *mc;
+    unsigned char* code;
+    float* resid;
+    unsigned char* ccode;
+    float* cresid;
 };
 
 unsigned linearize_grid(const IcpArgs& a, int n_cu) {
@@ -805,11 +597,13 @@ unsigned linearize_grid(const IcpArgs& a, int n_cu) {
     return (unsigned)std::max(1ll, std::min<long long>((n + kIcpWG - 1) / kIcpWG, (long long)std::max(n_cu, 1) * 4));
 }
 
-// The arguments of the linearise launches of one call, with the tables queued on the stream.
-int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, int flags, const void* depth,
-            const float* dm, const float* nm, unsigned char* code, float* resid, int n_cu, IcpArgs* out, unsigned* grid) {
+// The arguments of the linearise launches of one call, with the tables queued on the stream; with a
+// colour image (q is then its parameters) also the intensity image and the photo texels, by one prep
+// launch queued after ev_prep.
+int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, int flags, const Images& im,
+            const tsdf_icp_color_params_t* q, int n_cu, IcpArgs* out, unsigned* grid, hipEvent_t ev_prep = nullptr) {
     IcpArgs a{};
-    a.depth = depth;
+    a.depth = im.depth;
     a.dk = dk;
     a.inval = (flags & TSDF_DEPTH_INVALID_65535) ? 1 : 0;
     a.Hf = cam.Hf;
@@ -819,8 +613,8 @@ int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, i
     a.stride = p.stride;
     a.su = (cam.Wf + p.stride - 1) / p.stride;
     a.sv = (cam.Hf + p.stride - 1) / p.stride;
-    a.dm = dm;
-    a.nm = nm;
+    a.dm = im.dm;
+    a.nm = im.nm;
     const size_t nt = (size_t)cam.Wf + cam.Hf + cam.Wm + cam.Hm;
     TSDF_TRY(ensure(c, kBufTables, nt * sizeof(float)));
     float* t = (float*)c.buf[kBufTables];
@@ -838,26 +632,49 @@ int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, i
     a.cos_min = (float)p.cos_min;
     a.st = (const IcpState*)c.buf[kBufState];
     *grid = linearize_grid(a, n_cu);
-    TSDF_TRY(ensure(c, kBufPartial, (size_t)*grid * kIcpRec * sizeof(double)));
+    TSDF_TRY(ensure(c, kBufPartial, (size_t)*grid * (im.rgb ? 2 : 1) * kIcpRec * sizeof(double)));
     a.partial = (double*)c.buf[kBufPartial];
-    a.code = code;
-    a.resid = resid;
+    a.code = im.code;
+    a.resid = im.resid;
     hipLaunchKernelGGL(k_icp_tables, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c.stream, cam.Wf, cam.Hf, cam.Wm,
                        cam.Hm, cam.Kf[0], cam.Kf[4], cam.Kf[2], cam.Kf[5], cam.Km[0], cam.Km[4], cam.Km[2], cam.Km[5], t);
     TSDF_HIP(hipGetLastError());
     // pixels no lane visits (stride > 1) read code 0, residual 0
+    const size_t pf = (size_t)cam.Hf * cam.Wf, pm = (size_t)cam.Hm * cam.Wm;
     if (p.stride > 1) {
-        if (code) TSDF_HIP(hipMemsetAsync(code, 0, (size_t)cam.Hf * cam.Wf, c.stream));
-        if (resid) TSDF_HIP(hipMemsetAsync(resid, 0, (size_t)cam.Hf * cam.Wf * sizeof(float), c.stream));
+        if (im.code) TSDF_HIP(hipMemsetAsync(im.code, 0, pf, c.stream));
+        if (im.resid) TSDF_HIP(hipMemsetAsync(im.resid, 0, pf * sizeof(float), c.stream));
+    }
+    if (im.rgb) {
+        if (ev_prep) TSDF_HIP(hipEventRecord(ev_prep, c.stream));
+        TSDF_TRY(ensure(c, kBufFrameI, pf));
+        TSDF_TRY(ensure(c, kBufTexel, pm * sizeof(float4)));
+        a.fi = (const unsigned char*)c.buf[kBufFrameI];
+        a.tex = (const float4*)c.buf[kBufTexel];
+        a.color_max = q->color_max_diff;
+        a.ccode = im.ccode;
+        a.cresid = im.cresid;
+        hipLaunchKernelGGL(k_icp_photo_prep, dim3((unsigned)((std::max(pf, pm) + 255) / 256)), dim3(256), 0, c.stream, im.rgb,
+                           (int)pf, (unsigned char*)c.buf[kBufFrameI], im.mc, a.dm, a.Hm, a.Wm, (float4*)c.buf[kBufTexel]);
+        TSDF_HIP(hipGetLastError());
+        if (p.stride > 1) {
+            if (im.ccode) TSDF_HIP(hipMemsetAsync(im.ccode, 0, pf, c.stream));
+            if (im.cresid) TSDF_HIP(hipMemsetAsync(im.cresid, 0, pf * sizeof(float), c.stream));
+        }
     }
     *out = a;
     return TSDF_OK;
 }
 
+// One iteration: the linearise instance of the depth kind and of whether prepare() saw a colour
+// image, then the finish of the same kind.
 int launch_iteration(IcpCtx& c, const IcpArgs& a, unsigned grid, IcpRecord* rec, int solve, int last,
-                     const tsdf_icp_params_t& p, hipEvent_t ev_mid = nullptr, hipEvent_t ev_end = nullptr) {
-    if (a.dk == TSDF_DEPTH_U16_MM) hipLaunchKernelGGL(k_icp_linearize<TSDF_DEPTH_U16_MM>, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
-    else hipLaunchKernelGGL(k_icp_linearize<TSDF_DEPTH_F64_M>, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
+                     const tsdf_icp_params_t& p, const tsdf_icp_color_params_t* q, hipEvent_t ev_mid = nullptr,
+                     hipEvent_t ev_end = nullptr) {
+    const bool u16 = a.dk == TSDF_DEPTH_U16_MM, rgbd = a.fi != nullptr;
+    auto lin = rgbd ? (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, true> : k_icp_linearize<TSDF_DEPTH_F64_M, true>)
+                    : (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, false> : k_icp_linearize<TSDF_DEPTH_F64_M, false>);
+    hipLaunchKernelGGL(lin, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
     TSDF_HIP(hipGetLastError());
     if (ev_mid) TSDF_HIP(hipEventRecord(ev_mid, c.stream));
     FinishArgs f{};
@@ -870,7 +687,8 @@ int launch_iteration(IcpCtx& c, const IcpArgs& a, unsigned grid, IcpRecord* rec,
     f.min_inliers = p.min_inliers;
     f.eps_rot = p.eps_rot;
     f.eps_trans = p.eps_trans;
-    hipLaunchKernelGGL(k_icp_finish, dim3(1), dim3(kFinWG), 0, c.stream, f);
+    f.l2 = rgbd ? q->color_weight * q->color_weight : 0.0;
+    hipLaunchKernelGGL(rgbd ? k_icp_finish<true> : k_icp_finish<false>, dim3(1), dim3(kFinWG), 0, c.stream, f);
     TSDF_HIP(hipGetLastError());
     if (ev_end) TSDF_HIP(hipEventRecord(ev_end, c.stream));
     return TSDF_OK;
@@ -887,19 +705,27 @@ std::mutex g_dev_mu;
 
 // HIP-event times of the calling thread's last track on a handle with profiling on
 thread_local double g_track_ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, 0.0};
+thread_local double g_track_prep_ms = -1.0;  // the prep launch of its last RGB-D track
 
+// The four handle entry points.  rgbd: the raycast also writes the model's colour map, one prep
+// launch, and the colour instances of the two kernels; else color, q and cinfo are null.
 int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const double*, double, double, double, float*,
                                           float*, uint8_t*, int),
-          void* handle, const void* depth, int dk, int H, int W, const double* K, const double* pose_guess,
-          const tsdf_icp_params_t* p, double zn, double zf, double zs, double* out_pose, tsdf_track_info_t* info,
-          double* trajectory, int flags) {
+          void* handle, bool rgbd, const void* depth, int dk, const uint8_t* color, int H, int W, const double* K,
+          const double* pose_guess, const tsdf_icp_params_t* p, const tsdf_icp_color_params_t* q, double zn, double zf,
+          double zs, double* out_pose, tsdf_track_info_t* info, tsdf_track_color_info_t* cinfo, double* trajectory,
+          int flags) {
     Base& B = *S.b;
     if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
+    if (rgbd && !color) return set_error(TSDF_E_ARG, "null color image pointer");
     if (!K || !pose_guess) return set_error(TSDF_E_ARG, "null camera pointer");
     if (!out_pose) return set_error(TSDF_E_ARG, "null out_pose pointer");
     if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
     if (bad_size(H, W)) return set_error(TSDF_E_ARG, "bad image size %dx%d", H, W);
+    if (rgbd && (H < 4 || W < 4))
+        return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", H, W);
     TSDF_TRY(check_params(p));
+    if (rgbd) TSDF_TRY(check_color_params(q));
     if (!B.icp) {
         B.icp = new IcpCtx();
         B.icp->device = B.device;
@@ -910,16 +736,27 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
     TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
     TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
+    if (rgbd) TSDF_TRY(ensure(c, kBufModelC, px * 3));
     TSDF_TRY(ensure(c, kBufState, state_bytes(p->max_iter)));
-    const void* dd = depth;
+    Images im{};
+    im.depth = depth;
+    im.rgb = rgbd ? color : nullptr;
     if (!dev) {
-        const size_t nb = frame_bytes_depth(dk, H, W);
-        TSDF_TRY(ensure(c, kBufDepth, nb));
-        dd = c.buf[kBufDepth];
+        TSDF_TRY(ensure(c, kBufDepth, frame_bytes_depth(dk, H, W)));
+        im.depth = c.buf[kBufDepth];
+        if (rgbd) {
+            TSDF_TRY(ensure(c, kBufRgb, px * 3));
+            im.rgb = (const unsigned char*)c.buf[kBufRgb];
+        }
     }
-    // profiling on: events around the raycast, the setup and every launch of the iterations
+    im.dm = (const float*)c.buf[kBufModelD];
+    im.nm = (const float*)c.buf[kBufModelN];
+    im.mc = rgbd ? (const unsigned char*)c.buf[kBufModelC] : nullptr;
+    // profiling on: events around the raycast, the setup, the prep of an RGB-D track and every launch
+    // of the iterations
     const bool timed = B.prof.on;
-    std::vector<hipEvent_t> ev(timed ? 3 + 2 * (size_t)p->max_iter : 0, nullptr);
+    const size_t off = rgbd ? 1 : 0;  // the prep's event
+    std::vector<hipEvent_t> ev(timed ? 3 + off + 2 * (size_t)p->max_iter : 0, nullptr);
     struct EvGuard {
         std::vector<hipEvent_t>& e;
         ~EvGuard() {
@@ -931,10 +768,13 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     if (timed) TSDF_HIP(hipEventRecord(ev[0], c.stream));
     // the model maps: the handle's own raycast at pose_guess (it runs the deferred frames first and
     // refuses what a raycast refuses)
-    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN], nullptr,
-                  TSDF_DEVICE_PTRS | TSDF_ASYNC));
+    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN],
+                  rgbd ? (uint8_t*)c.buf[kBufModelC] : nullptr, TSDF_DEVICE_PTRS | TSDF_ASYNC));
     if (timed) TSDF_HIP(hipEventRecord(ev[1], c.stream));
-    if (!dev) TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
+    if (!dev) {
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
+        if (rgbd) TSDF_HIP(hipMemcpyAsync(c.buf[kBufRgb], color, px * 3, hipMemcpyHostToDevice, c.stream));
+    }
     char* sb = (char*)c.buf[kBufState];
     IcpRecord* rec = (IcpRecord*)(sb + kRecOff);
     hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)nullptr);
@@ -942,12 +782,11 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     Cameras cam{H, W, H, W, K, K, pose_guess};
     IcpArgs a;
     unsigned grid;
-    TSDF_TRY(prepare(c, cam, *p, dk, flags, dd, (const float*)c.buf[kBufModelD], (const float*)c.buf[kBufModelN], nullptr,
-                     nullptr, B.n_cu, &a, &grid));
-    if (timed) TSDF_HIP(hipEventRecord(ev[2], c.stream));
+    TSDF_TRY(prepare(c, cam, *p, dk, flags, im, q, B.n_cu, &a, &grid, timed && rgbd ? ev[2] : nullptr));
+    if (timed) TSDF_HIP(hipEventRecord(ev[2 + off], c.stream));
     for (int it = 0; it < p->max_iter; ++it)
-        TSDF_TRY(launch_iteration(c, a, grid, rec + it, 1, it == p->max_iter - 1, *p,
-                                  timed ? ev[3 + 2 * it] : nullptr, timed ? ev[4 + 2 * it] : nullptr));
+        TSDF_TRY(launch_iteration(c, a, grid, rec + it, 1, it == p->max_iter - 1, *p, q,
+                                  timed ? ev[3 + off + 2 * it] : nullptr, timed ? ev[4 + off + 2 * it] : nullptr));
     // one synchronisation, one copy back
     std::vector<char> host(state_bytes(p->max_iter));
     TSDF_HIP(hipMemcpyAsync(host.data(), sb, host.size(), hipMemcpyDeviceToHost, c.stream));
@@ -956,15 +795,18 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     const IcpRecord* hr = (const IcpRecord*)(host.data() + kRecOff);
     const int iters = std::min(std::max(st->iters, 0), p->max_iter);
     if (timed) {
-        double ms[5] = {0, 0, 0, 0, 0};  // raycast, setup, linearise, finish (iterations run), fall-through launches
+        // raycast, setup, linearise, finish (iterations run), fall-through launches; and the prep launch
+        double ms[5] = {0, 0, 0, 0, 0}, prep = 0.0;
         for (size_t i = 0; i + 1 < ev.size(); ++i) {
             float x = 0.0f;
             TSDF_HIP(hipEventElapsedTime(&x, ev[i], ev[i + 1]));
-            const int it = i < 2 ? 0 : (int)(i - 2) / 2;
-            ms[i < 2 ? i : (it >= iters ? 4 : 2 + (int)(i - 2) % 2)] += x;
+            if (i < 2) ms[i] += x;
+            else if (i < 2 + off) prep += x;
+            else ms[(int)(i - 2 - off) / 2 >= iters ? 4 : 2 + (int)(i - 2 - off) % 2] += x;
         }
         for (int i = 0; i < 5; ++i) g_track_ms[i] = ms[i];
         g_track_ms[5] = (double)iters;
+        if (rgbd) g_track_prep_ms = prep;
     }
     // out_pose = pose_guess * M, f64, three-term sums left to right
     for (int r = 0; r < 4; ++r)
@@ -973,17 +815,25 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
             for (int e = 0; e < 4; ++e) x += pose_guess[4 * r + e] * st->M[4 * e + k];
             out_pose[4 * r + k] = x;
         }
+    if (info) memset(info, 0, sizeof(*info));
+    if (cinfo) memset(cinfo, 0, sizeof(*cinfo));
     if (info) {
-        memset(info, 0, sizeof(*info));
         info->status = st->status;
         info->iterations = iters;
-        if (iters > 0) {
-            const IcpRecord& L = hr[iters - 1];
+    }
+    if (iters > 0) {
+        const IcpRecord& L = hr[iters - 1];
+        if (info) {
             info->inliers = L.inliers;
             info->candidates = L.candidates;
             info->rms = L.inliers > 0 ? std::sqrt(L.sums[27] / (double)L.inliers) : 0.0;
             info->w_norm = L.w_norm;
             info->t_norm = L.t_norm;
+        }
+        if (cinfo) {
+            cinfo->color_inliers = L.c_inliers;
+            cinfo->color_candidates = L.c_candidates;
+            cinfo->color_rms = L.c_inliers > 0 ? std::sqrt(L.csums[27] / (double)L.c_inliers) : 0.0;
         }
     }
     if (trajectory) {
@@ -1028,218 +878,25 @@ int device_context(int device, IcpCtx** out, int* n_cu) {
     return TSDF_OK;
 }
 
-// ---- the photometric term's host side (§7f) ------------------------------------------------------
-int check_color_params(const tsdf_icp_color_params_t* q) {
-    if (!q) return set_error(TSDF_E_ARG, "null color params pointer");
-    if (!(q->color_weight >= 0.0) || !std::isfinite(q->color_weight))
-        return set_error(TSDF_E_ARG, "color_weight must be finite and >= 0 (got %g)", q->color_weight);
-    if (!(q->color_max_diff > 0.0f)) return set_error(TSDF_E_ARG, "color_max_diff must be > 0 (got %g)", (double)q->color_max_diff);
-    return TSDF_OK;
-}
-
-// From the arguments prepare() made: the wider partial records, the intensity image and the photo
-// texels (one prep launch queued on the stream).  rgb and mc are device pointers.
-int prepare_rgbd(IcpCtx& c, const IcpArgs& a, unsigned grid, int stride, const unsigned char* rgb, const unsigned char* mc,
-                 const tsdf_icp_color_params_t& q, unsigned char* ccode, float* cresid, RgbdArgs* out) {
-    const size_t pf = (size_t)a.Hf * a.Wf, pm = (size_t)a.Hm * a.Wm;
-    TSDF_TRY(ensure(c, kBufFrameI, pf));
-    TSDF_TRY(ensure(c, kBufTexel, pm * sizeof(float4)));
-    TSDF_TRY(ensure(c, kBufPartial, (size_t)grid * kRgbdRec * sizeof(double)));
-    RgbdArgs A{};
-    A.g = a;
-    A.g.partial = (double*)c.buf[kBufPartial];
-    A.fi = (const unsigned char*)c.buf[kBufFrameI];
-    A.tex = (const float4*)c.buf[kBufTexel];
-    A.color_max = q.color_max_diff;
-    A.ccode = ccode;
-    A.cresid = cresid;
-    hipLaunchKernelGGL(k_icp_photo_prep, dim3((unsigned)((std::max(pf, pm) + 255) / 256)), dim3(256), 0, c.stream, rgb, (int)pf,
-                       (unsigned char*)c.buf[kBufFrameI], mc, a.dm, a.Hm, a.Wm, (float4*)c.buf[kBufTexel]);
-    TSDF_HIP(hipGetLastError());
-    if (stride > 1) {
-        if (ccode) TSDF_HIP(hipMemsetAsync(ccode, 0, pf, c.stream));
-        if (cresid) TSDF_HIP(hipMemsetAsync(cresid, 0, pf * sizeof(float), c.stream));
-    }
-    *out = A;
-    return TSDF_OK;
-}
-
-int launch_iteration_rgbd(IcpCtx& c, const RgbdArgs& A, unsigned grid, IcpRecordRgbd* rec, int solve, int last,
-                          const tsdf_icp_params_t& p, double color_weight, hipEvent_t ev_mid = nullptr,
-                          hipEvent_t ev_end = nullptr) {
-    if (A.g.dk == TSDF_DEPTH_U16_MM)
-        hipLaunchKernelGGL(k_icp_linearize_rgbd<TSDF_DEPTH_U16_MM>, dim3(grid), dim3(kIcpWG), 0, c.stream, A);
-    else hipLaunchKernelGGL(k_icp_linearize_rgbd<TSDF_DEPTH_F64_M>, dim3(grid), dim3(kIcpWG), 0, c.stream, A);
-    TSDF_HIP(hipGetLastError());
-    if (ev_mid) TSDF_HIP(hipEventRecord(ev_mid, c.stream));
-    FinishRgbdArgs f{};
-    f.partial = A.g.partial;
-    f.n_partial = (int)grid;
-    f.st = (IcpState*)c.buf[kBufState];
-    f.rec = rec;
-    f.solve = solve;
-    f.last = last;
-    f.min_inliers = p.min_inliers;
-    f.eps_rot = p.eps_rot;
-    f.eps_trans = p.eps_trans;
-    f.l2 = color_weight * color_weight;
-    hipLaunchKernelGGL(k_icp_finish_rgbd, dim3(1), dim3(kFinWG), 0, c.stream, f);
-    TSDF_HIP(hipGetLastError());
-    if (ev_end) TSDF_HIP(hipEventRecord(ev_end, c.stream));
-    return TSDF_OK;
-}
-
-size_t state_bytes_rgbd(int n_rec) { return kRecOff + sizeof(IcpRecordRgbd) * (size_t)n_rec; }
-
-thread_local double g_track_prep_ms = -1.0;  // of the calling thread's last RGB-D track with profiling on
-
-// track() with the colour term: the raycast also writes the model's colour map, one prep launch, and
-// the RGB-D kernels in place of the geometric pair.
-int track_rgbd(const RaySource& S, int (*cast)(void*, int, int, const double*, const double*, double, double, double,
-                                               float*, float*, uint8_t*, int),
-               void* handle, const void* depth, int dk, const uint8_t* color, int H, int W, const double* K,
-               const double* pose_guess, const tsdf_icp_params_t* p, const tsdf_icp_color_params_t* q, double zn,
-               double zf, double zs, double* out_pose, tsdf_track_info_t* info, tsdf_track_color_info_t* cinfo,
-               double* trajectory, int flags) {
-    Base& B = *S.b;
+// The two handle-less entry points: one linearisation at rel_pose, no solve.  rgbd: sums[56] and
+// counts[4], else sums[28] and counts[2], and color, model_colors, q and the colour maps are null.
+int linearize_once(bool rgbd, int device, const void* depth, int dk, const uint8_t* color, int Hf, int Wf, const double* Kf,
+                   const double* rel_pose, const float* model_depth, const float* model_normals, const uint8_t* model_colors,
+                   int Hm, int Wm, const double* Km, const double* model_pose, const tsdf_icp_params_t* params,
+                   const tsdf_icp_color_params_t* q, double* sums, int64_t* counts, uint8_t* code, float* residual,
+                   uint8_t* color_code, float* color_residual, int flags) {
     if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
-    if (!color) return set_error(TSDF_E_ARG, "null color image pointer");
-    if (!K || !pose_guess) return set_error(TSDF_E_ARG, "null camera pointer");
-    if (!out_pose) return set_error(TSDF_E_ARG, "null out_pose pointer");
-    if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
-    if (bad_size(H, W)) return set_error(TSDF_E_ARG, "bad image size %dx%d", H, W);
-    if (H < 4 || W < 4) return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", H, W);
-    TSDF_TRY(check_params(p));
-    TSDF_TRY(check_color_params(q));
-    if (!B.icp) {
-        B.icp = new IcpCtx();
-        B.icp->device = B.device;
-        B.icp->stream = B.stream;
-    }
-    IcpCtx& c = *B.icp;
-    const size_t px = (size_t)H * W;
-    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
-    TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
-    TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
-    TSDF_TRY(ensure(c, kBufModelC, px * 3));
-    TSDF_TRY(ensure(c, kBufState, state_bytes_rgbd(p->max_iter)));
-    const void* dd = depth;
-    const unsigned char* dc = color;
-    if (!dev) {
-        TSDF_TRY(ensure(c, kBufDepth, frame_bytes_depth(dk, H, W)));
-        TSDF_TRY(ensure(c, kBufRgb, px * 3));
-        dd = c.buf[kBufDepth];
-        dc = (const unsigned char*)c.buf[kBufRgb];
-    }
-    // profiling on: events around the raycast, the setup, the prep and every launch of the iterations
-    const bool timed = B.prof.on;
-    std::vector<hipEvent_t> ev(timed ? 4 + 2 * (size_t)p->max_iter : 0, nullptr);
-    struct EvGuard {
-        std::vector<hipEvent_t>& e;
-        ~EvGuard() {
-            for (auto x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } ev_guard{ev};
-    for (auto& e : ev) TSDF_HIP(hipEventCreate(&e));
-    if (timed) TSDF_HIP(hipEventRecord(ev[0], c.stream));
-    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN],
-                  (uint8_t*)c.buf[kBufModelC], TSDF_DEVICE_PTRS | TSDF_ASYNC));
-    if (timed) TSDF_HIP(hipEventRecord(ev[1], c.stream));
-    if (!dev) {
-        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
-        TSDF_HIP(hipMemcpyAsync(c.buf[kBufRgb], color, px * 3, hipMemcpyHostToDevice, c.stream));
-    }
-    char* sb = (char*)c.buf[kBufState];
-    IcpRecordRgbd* rec = (IcpRecordRgbd*)(sb + kRecOff);
-    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)nullptr);
-    TSDF_HIP(hipGetLastError());
-    Cameras cam{H, W, H, W, K, K, pose_guess};
-    IcpArgs a;
-    RgbdArgs A;
-    unsigned grid;
-    TSDF_TRY(prepare(c, cam, *p, dk, flags, dd, (const float*)c.buf[kBufModelD], (const float*)c.buf[kBufModelN], nullptr,
-                     nullptr, B.n_cu, &a, &grid));
-    if (timed) TSDF_HIP(hipEventRecord(ev[2], c.stream));
-    TSDF_TRY(prepare_rgbd(c, a, grid, p->stride, dc, (const unsigned char*)c.buf[kBufModelC], *q, nullptr, nullptr, &A));
-    if (timed) TSDF_HIP(hipEventRecord(ev[3], c.stream));
-    for (int it = 0; it < p->max_iter; ++it)
-        TSDF_TRY(launch_iteration_rgbd(c, A, grid, rec + it, 1, it == p->max_iter - 1, *p, q->color_weight,
-                                       timed ? ev[4 + 2 * it] : nullptr, timed ? ev[5 + 2 * it] : nullptr));
-    std::vector<char> host(state_bytes_rgbd(p->max_iter));
-    TSDF_HIP(hipMemcpyAsync(host.data(), sb, host.size(), hipMemcpyDeviceToHost, c.stream));
-    TSDF_HIP(hipStreamSynchronize(c.stream));
-    const IcpState* st = (const IcpState*)(host.data() + kStateOff);
-    const IcpRecordRgbd* hr = (const IcpRecordRgbd*)(host.data() + kRecOff);
-    const int iters = std::min(std::max(st->iters, 0), p->max_iter);
-    if (timed) {
-        double ms[5] = {0, 0, 0, 0, 0}, prep = 0.0;  // as track()'s, and the prep launch
-        for (size_t i = 0; i + 1 < ev.size(); ++i) {
-            float x = 0.0f;
-            TSDF_HIP(hipEventElapsedTime(&x, ev[i], ev[i + 1]));
-            if (i == 2) {
-                prep += x;
-                continue;
-            }
-            const int it = i < 3 ? 0 : (int)(i - 3) / 2;
-            ms[i < 2 ? i : (it >= iters ? 4 : 2 + (int)(i - 3) % 2)] += x;
-        }
-        for (int i = 0; i < 5; ++i) g_track_ms[i] = ms[i];
-        g_track_ms[5] = (double)iters;
-        g_track_prep_ms = prep;
-    }
-    for (int r = 0; r < 4; ++r)
-        for (int k = 0; k < 4; ++k) {
-            double x = 0.0;
-            for (int e = 0; e < 4; ++e) x += pose_guess[4 * r + e] * st->M[4 * e + k];
-            out_pose[4 * r + k] = x;
-        }
-    if (info) memset(info, 0, sizeof(*info));
-    if (cinfo) memset(cinfo, 0, sizeof(*cinfo));
-    if (info) {
-        info->status = st->status;
-        info->iterations = iters;
-    }
-    if (iters > 0) {
-        const IcpRecordRgbd& L = hr[iters - 1];
-        if (info) {
-            info->inliers = L.inliers;
-            info->candidates = L.candidates;
-            info->rms = L.inliers > 0 ? std::sqrt(L.sums[27] / (double)L.inliers) : 0.0;
-            info->w_norm = L.w_norm;
-            info->t_norm = L.t_norm;
-        }
-        if (cinfo) {
-            cinfo->color_inliers = L.c_inliers;
-            cinfo->color_candidates = L.c_candidates;
-            cinfo->color_rms = L.c_inliers > 0 ? std::sqrt(L.csums[27] / (double)L.c_inliers) : 0.0;
-        }
-    }
-    if (trajectory) {
-        memset(trajectory, 0, sizeof(double) * 16 * ((size_t)p->max_iter + 1));
-        for (int i = 0; i < 4; ++i) trajectory[5 * i] = 1.0;
-        for (int i = 0; i < iters; ++i) memcpy(trajectory + 16 * (i + 1), hr[i].M, sizeof(double) * 16);
-    }
-    return TSDF_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, int Wf, const double Kf[9],
-                       const double rel_pose[16], const float* model_depth, const float* model_normals, int Hm, int Wm,
-                       const double Km[9], const double model_pose[16], const tsdf_icp_params_t* params, double sums[28],
-                       int64_t counts[2], uint8_t* code, float* residual, int flags) {
-    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
-    if (!model_depth || !model_normals) return set_error(TSDF_E_ARG, "null model map pointer");
+    if (rgbd && !color) return set_error(TSDF_E_ARG, "null color image pointer");
+    if (!model_depth || !model_normals || (rgbd && !model_colors)) return set_error(TSDF_E_ARG, "null model map pointer");
     if (!Kf || !Km || !rel_pose || !model_pose) return set_error(TSDF_E_ARG, "null camera pointer");
     if (!sums || !counts) return set_error(TSDF_E_ARG, "null sums / counts pointer");
-    if (depth_kind != TSDF_DEPTH_U16_MM && depth_kind != TSDF_DEPTH_F64_M)
-        return set_error(TSDF_E_ARG, "bad depth_kind %d", depth_kind);
+    if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
     if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
     if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
+    if (rgbd && (Hm < 4 || Wm < 4))
+        return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", Hm, Wm);
     TSDF_TRY(check_params(params));
+    if (rgbd) TSDF_TRY(check_color_params(q));
     IcpCtx* cp;
     int n_cu;
     TSDF_TRY(device_context(device, &cp, &n_cu));
@@ -1248,100 +905,14 @@ int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, in
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
     const size_t pf = (size_t)Hf * Wf, pm = (size_t)Hm * Wm;
     TSDF_TRY(ensure(c, kBufState, state_bytes(1)));
-    const void* dd = depth;
-    const float *dm = model_depth, *nm = model_normals;
-    unsigned char* dcode = code;
-    float* dres = residual;
-    if (!dev) {
-        TSDF_TRY(ensure(c, kBufDepth, frame_bytes_depth(depth_kind, Hf, Wf)));
-        TSDF_TRY(ensure(c, kBufModelD, pm * sizeof(float)));
-        TSDF_TRY(ensure(c, kBufModelN, pm * 3 * sizeof(float)));
-        if (code) TSDF_TRY(ensure(c, kBufCode, pf));
-        if (residual) TSDF_TRY(ensure(c, kBufResid, pf * sizeof(float)));
-        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(depth_kind, Hf, Wf), hipMemcpyHostToDevice, c.stream));
-        TSDF_HIP(hipMemcpyAsync(c.buf[kBufModelD], model_depth, pm * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        TSDF_HIP(hipMemcpyAsync(c.buf[kBufModelN], model_normals, pm * 3 * sizeof(float), hipMemcpyHostToDevice, c.stream));
-        dd = c.buf[kBufDepth];
-        dm = (const float*)c.buf[kBufModelD];
-        nm = (const float*)c.buf[kBufModelN];
-        dcode = code ? (unsigned char*)c.buf[kBufCode] : nullptr;
-        dres = residual ? (float*)c.buf[kBufResid] : nullptr;
-    }
-    char* sb = (char*)c.buf[kBufState];
-    TSDF_HIP(hipMemcpyAsync(sb + kPoseOff, rel_pose, sizeof(double) * 16, hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)(sb + kPoseOff));
-    TSDF_HIP(hipGetLastError());
-    Cameras cam{Hf, Wf, Hm, Wm, Kf, Km, model_pose};
-    IcpArgs a;
-    unsigned grid;
-    TSDF_TRY(prepare(c, cam, *params, depth_kind, flags, dd, dm, nm, dcode, dres, n_cu, &a, &grid));
-    TSDF_TRY(launch_iteration(c, a, grid, (IcpRecord*)(sb + kRecOff), 0, 1, *params));
-    IcpRecord rec;
-    TSDF_HIP(hipMemcpyAsync(&rec, sb + kRecOff, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
-    if (!dev) {
-        if (code) TSDF_HIP(hipMemcpyAsync(code, dcode, pf, hipMemcpyDeviceToHost, c.stream));
-        if (residual) TSDF_HIP(hipMemcpyAsync(residual, dres, pf * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-    }
-    TSDF_HIP(hipStreamSynchronize(c.stream));
-    memcpy(sums, rec.sums, sizeof(double) * 28);
-    counts[0] = rec.inliers;
-    counts[1] = rec.candidates;
-    return TSDF_OK;
-}
-
-int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
-                     const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
-                     double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
-    if (!h) return set_error(TSDF_E_ARG, "null handle");
-    RaySource S;
-    TSDF_TRY(dense_ray_source(h, &S));
-    return track(S, cast_dense, h, depth, depth_kind, height, width, K, pose_guess, params, z_near, z_far, z_step, out_pose,
-                 info, trajectory, flags);
-}
-
-int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
-                    const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
-                    double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
-    if (!h) return set_error(TSDF_E_ARG, "null handle");
-    RaySource S;
-    TSDF_TRY(hash_ray_source(h, &S));
-    return track(S, cast_hash, h, depth, depth_kind, height, width, K, pose_guess, params, z_near, z_far, z_step, out_pose,
-                 info, trajectory, flags);
-}
-
-int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const uint8_t* color, int Hf, int Wf,
-                            const double Kf[9], const double rel_pose[16], const float* model_depth,
-                            const float* model_normals, const uint8_t* model_colors, int Hm, int Wm, const double Km[9],
-                            const double model_pose[16], const tsdf_icp_params_t* params,
-                            const tsdf_icp_color_params_t* color_params, double sums[56], int64_t counts[4], uint8_t* code,
-                            float* residual, uint8_t* color_code, float* color_residual, int flags) {
-    if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
-    if (!color) return set_error(TSDF_E_ARG, "null color image pointer");
-    if (!model_depth || !model_normals || !model_colors) return set_error(TSDF_E_ARG, "null model map pointer");
-    if (!Kf || !Km || !rel_pose || !model_pose) return set_error(TSDF_E_ARG, "null camera pointer");
-    if (!sums || !counts) return set_error(TSDF_E_ARG, "null sums / counts pointer");
-    if (depth_kind != TSDF_DEPTH_U16_MM && depth_kind != TSDF_DEPTH_F64_M)
-        return set_error(TSDF_E_ARG, "bad depth_kind %d", depth_kind);
-    if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
-    if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
-    if (Hm < 4 || Wm < 4) return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", Hm, Wm);
-    TSDF_TRY(check_params(params));
-    TSDF_TRY(check_color_params(color_params));
-    IcpCtx* cp;
-    int n_cu;
-    TSDF_TRY(device_context(device, &cp, &n_cu));
-    IcpCtx& c = *cp;
-    std::lock_guard<std::mutex> lk(c.mu);
-    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
-    const size_t pf = (size_t)Hf * Wf, pm = (size_t)Hm * Wm;
-    TSDF_TRY(ensure(c, kBufState, state_bytes_rgbd(1)));
-    // host images go through the context's buffers: {caller's pointer, buffer, bytes}
+    // host images go through the context's buffers: {caller's pointer, buffer, bytes}; a null row
+    // (the colour rows of the geometric call, an output not asked for) is skipped
     struct Img {
         const void* host;
         int buf;
         size_t bytes;
     };
-    const Img in[5] = {{depth, kBufDepth, frame_bytes_depth(depth_kind, Hf, Wf)}, {color, kBufRgb, pf * 3},
+    const Img in[5] = {{depth, kBufDepth, frame_bytes_depth(dk, Hf, Wf)}, {color, kBufRgb, pf * 3},
                        {model_depth, kBufModelD, pm * sizeof(float)}, {model_normals, kBufModelN, pm * 3 * sizeof(float)},
                        {model_colors, kBufModelC, pm * 3}};
     const Img outs[4] = {{code, kBufCode, pf}, {residual, kBufResid, pf * sizeof(float)}, {color_code, kBufCodeC, pf},
@@ -1350,7 +921,7 @@ int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const
     void* dout[4];
     for (int i = 0; i < 5; ++i) {
         din[i] = in[i].host;
-        if (dev) continue;
+        if (dev || !in[i].host) continue;
         TSDF_TRY(ensure(c, in[i].buf, in[i].bytes));
         TSDF_HIP(hipMemcpyAsync(c.buf[in[i].buf], in[i].host, in[i].bytes, hipMemcpyHostToDevice, c.stream));
         din[i] = c.buf[in[i].buf];
@@ -1366,27 +937,71 @@ int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const
     hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)(sb + kPoseOff));
     TSDF_HIP(hipGetLastError());
     Cameras cam{Hf, Wf, Hm, Wm, Kf, Km, model_pose};
+    const Images im{din[0], (const float*)din[2], (const float*)din[3], (const unsigned char*)din[1],
+                    (const unsigned char*)din[4], (unsigned char*)dout[0], (float*)dout[1], (unsigned char*)dout[2],
+                    (float*)dout[3]};
     IcpArgs a;
-    RgbdArgs A;
     unsigned grid;
-    TSDF_TRY(prepare(c, cam, *params, depth_kind, flags, din[0], (const float*)din[2], (const float*)din[3],
-                     (unsigned char*)dout[0], (float*)dout[1], n_cu, &a, &grid));
-    TSDF_TRY(prepare_rgbd(c, a, grid, params->stride, (const unsigned char*)din[1], (const unsigned char*)din[4],
-                          *color_params, (unsigned char*)dout[2], (float*)dout[3], &A));
-    TSDF_TRY(launch_iteration_rgbd(c, A, grid, (IcpRecordRgbd*)(sb + kRecOff), 0, 1, *params, color_params->color_weight));
-    IcpRecordRgbd rec;
+    TSDF_TRY(prepare(c, cam, *params, dk, flags, im, q, n_cu, &a, &grid));
+    TSDF_TRY(launch_iteration(c, a, grid, (IcpRecord*)(sb + kRecOff), 0, 1, *params, q));
+    IcpRecord rec;
     TSDF_HIP(hipMemcpyAsync(&rec, sb + kRecOff, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
     if (!dev)
         for (int i = 0; i < 4; ++i)
             if (outs[i].host) TSDF_HIP(hipMemcpyAsync(const_cast<void*>(outs[i].host), dout[i], outs[i].bytes, hipMemcpyDeviceToHost, c.stream));
     TSDF_HIP(hipStreamSynchronize(c.stream));
     memcpy(sums, rec.sums, sizeof(double) * 28);
-    memcpy(sums + 28, rec.csums, sizeof(double) * 28);
     counts[0] = rec.inliers;
     counts[1] = rec.candidates;
-    counts[2] = rec.c_inliers;
-    counts[3] = rec.c_candidates;
+    if (rgbd) {
+        memcpy(sums + 28, rec.csums, sizeof(double) * 28);
+        counts[2] = rec.c_inliers;
+        counts[3] = rec.c_candidates;
+    }
     return TSDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, int Wf, const double Kf[9],
+                       const double rel_pose[16], const float* model_depth, const float* model_normals, int Hm, int Wm,
+                       const double Km[9], const double model_pose[16], const tsdf_icp_params_t* params, double sums[28],
+                       int64_t counts[2], uint8_t* code, float* residual, int flags) {
+    return linearize_once(false, device, depth, depth_kind, nullptr, Hf, Wf, Kf, rel_pose, model_depth, model_normals, nullptr,
+                          Hm, Wm, Km, model_pose, params, nullptr, sums, counts, code, residual, nullptr, nullptr, flags);
+}
+
+int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const uint8_t* color, int Hf, int Wf,
+                            const double Kf[9], const double rel_pose[16], const float* model_depth,
+                            const float* model_normals, const uint8_t* model_colors, int Hm, int Wm, const double Km[9],
+                            const double model_pose[16], const tsdf_icp_params_t* params,
+                            const tsdf_icp_color_params_t* color_params, double sums[56], int64_t counts[4], uint8_t* code,
+                            float* residual, uint8_t* color_code, float* color_residual, int flags) {
+    return linearize_once(true, device, depth, depth_kind, color, Hf, Wf, Kf, rel_pose, model_depth, model_normals,
+                          model_colors, Hm, Wm, Km, model_pose, params, color_params, sums, counts, code, residual, color_code,
+                          color_residual, flags);
+}
+
+int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                     const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
+                     double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return track(S, cast_dense, h, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
+                 z_far, z_step, out_pose, info, nullptr, trajectory, flags);
+}
+
+int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                    const double pose_guess[16], const tsdf_icp_params_t* params, double z_near, double z_far,
+                    double z_step, double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return track(S, cast_hash, h, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
+                 z_far, z_step, out_pose, info, nullptr, trajectory, flags);
 }
 
 int tsdf_dense_track_rgbd(tsdf_dense_t* h, const void* depth, int depth_kind, const uint8_t* color, int height, int width,
@@ -1397,8 +1012,8 @@ int tsdf_dense_track_rgbd(tsdf_dense_t* h, const void* depth, int depth_kind, co
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(dense_ray_source(h, &S));
-    return track_rgbd(S, cast_dense, h, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
-                      z_far, z_step, out_pose, info, color_info, trajectory, flags);
+    return track(S, cast_dense, h, true, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+                 z_far, z_step, out_pose, info, color_info, trajectory, flags);
 }
 
 int tsdf_hash_track_rgbd(tsdf_hash_t* h, const void* depth, int depth_kind, const uint8_t* color, int height, int width,
@@ -1409,8 +1024,8 @@ int tsdf_hash_track_rgbd(tsdf_hash_t* h, const void* depth, int depth_kind, cons
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(hash_ray_source(h, &S));
-    return track_rgbd(S, cast_hash, h, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
-                      z_far, z_step, out_pose, info, color_info, trajectory, flags);
+    return track(S, cast_hash, h, true, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+                 z_far, z_step, out_pose, info, color_info, trajectory, flags);
 }
 
 int tsdf_track_last_prep_ms(double* ms) {
