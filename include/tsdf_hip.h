@@ -276,7 +276,8 @@ int tsdf_dense_raycast(tsdf_dense_t* h, int height, int width, const double K[9]
                        const double cam_pose[16], double z_near, double z_far, double z_step,
                        float* depth, float* normals, uint8_t* colors, int flags);
 /* Track a depth frame against the fused model (not in the reference): frame-to-model
- * point-to-plane ICP, single resolution, geometry only.  The model maps are this handle's own
+ * point-to-plane ICP, single resolution, geometry only (tsdf_dense_track_rgbd adds colour;
+ * tsdf_dense_track_sdf aligns to the volume without a raycast).  The model maps are this handle's own
  * raycast (depth and normals, height x width through K, with z_near / z_far / z_step as there) at
  * pose_guess (camera-to-world); the frame (depth of depth_kind, height x width through the same K;
  * TSDF_DEPTH_INVALID_65535 is honoured; a host pointer, or a device pointer with TSDF_DEVICE_PTRS)
@@ -297,6 +298,50 @@ int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int hei
                      const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
                      double z_near, double z_far, double z_step, double out_pose[16],
                      tsdf_track_info_t* info, double* trajectory, int flags);
+/* Track a depth frame against the volume itself (Bylow et al., RSS 2013): point-to-SDF
+ * alignment.  The stored tsdf is a signed distance field, so the frame's points are aligned to it
+ * directly: minimise the sum of sdf(pose_guess * M * p)^2 with the trilinear interpolant of the
+ * stored tsdf and its gradient.  No raycast is queued, no live bits are computed and no model maps
+ * are allocated; no frame normal is needed, so the last row and column take part.  Arguments, the
+ * iteration (linearise, solve, M <- E(xi) M from M_0 = I, one synchronisation), out_pose, info,
+ * trajectory, lost, flags and determinism are tsdf_dense_track's, without the z range; one
+ * linearisation is tsdf_dense_sdf_linearize's.  params->cos_min is validated and otherwise unused.
+ * With profiling on, tsdf_track_last_ms reports 0 for the raycast.  TSDF_E_ARG: what
+ * tsdf_dense_track refuses, but for the z arguments. */
+int tsdf_dense_track_sdf(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width,
+                         const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                         double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags);
+/* One linearisation of the point-to-SDF alignment on this handle's volume, at
+ * pose_guess G (camera-to-world) and rel_pose M (frame camera to the guess camera's frame), rounded
+ * to f32 by the kernel.  Host side, in f64, each value rounded to f32 once: Qr = R_G / vs, Qo =
+ * (t_G - f64(origin)) / vs, Rg = R_G, s = trunc / vs, trunc, dist_max and the pixel tables.  Per
+ * sampled pixel (params->stride), every operation a separately rounded f32 operation, three-term
+ * sums as (a + b) + c: the depth d as in tsdf_icp_linearize (code 0 without one); p = M (x_u d, y_v d,
+ * d); the index-space point q = Qr p + Qo, i0 = floor(q), t = q - i0; the cell i0 + {0,1}^3 is not
+ * inside this handle's volume (the raycast's rule): code 2; a corner has weight <= 0 (a hash voxel
+ * without an entry has weight 0): 3; a corner has |tsdf| >= 1, the truncated plateau: 4; f the
+ * trilinear value and g the gradient of the interpolant as the raycast forms them; r = -(trunc f);
+ * |r| > dist_max or g exactly zero: 5; else the inlier, 6, with n_i = s ((Rg_0i g_x + Rg_1i g_y) +
+ * Rg_2i g_z), the metric gradient in the guess camera's frame (towards positive tsdf, not
+ * normalised), and the row J = (p x n, n).  sums, counts (inliers; candidates = codes 2..6), code
+ * and residual, the pointers (host, or all device with TSDF_DEVICE_PTRS) and the determinism are
+ * tsdf_icp_linearize's; the call runs on the handle's stream after its deferred frames, and
+ * synchronises.  Restated by tests/sdf_ref.py.  TSDF_E_ARG: a NULL depth / K / rel_pose /
+ * pose_guess / params / sums / counts, a bad image size, depth_kind or parameter, a cyclic column
+ * shard. */
+int tsdf_dense_sdf_linearize(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width,
+                             const double K[9], const double rel_pose[16], const double pose_guess[16],
+                             const tsdf_icp_params_t* params, double sums[28], int64_t counts[2],
+                             uint8_t* code, float* residual, int flags);
+/* The signed distance and its gradient at n world points (points: n x 3 f64), by the same cell:
+ * q_a = f32((P_a - f64(origin_a)) / vs), then the cell tests above.  code (n u8): 2, 3, 4 or 6;
+ * sdf (n f32): trunc f, metres; grad (n x 3 f32): s g in world axes, metres per metre, not
+ * normalised.  Value and gradient are written for codes 4 and 6, zeros otherwise.  Any output
+ * pointer may be NULL.  Host pointers, or all device pointers with TSDF_DEVICE_PTRS.  Deferred
+ * frames run first; synchronous.  TSDF_E_ARG: n < 0 or >= 2^31, NULL points with n > 0, a cyclic
+ * column shard. */
+int tsdf_dense_sample(tsdf_dense_t* h, const double* points, int64_t n, float* sdf, float* grad,
+                      uint8_t* code, int flags);
 /* tsdf_dense_track with a photometric term: where the view holds one plane, the
  * geometry cannot see the two in-plane translations and the rotation about the normal; the colour
  * can.  color: the frame's RGB8 image, height x width x 3 (a host pointer, or a device pointer with
@@ -412,8 +457,20 @@ int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int heigh
                     const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
                     double z_near, double z_far, double z_step, double out_pose[16],
                     tsdf_track_info_t* info, double* trajectory, int flags);
+/* tsdf_dense_track_sdf, tsdf_dense_sdf_linearize and tsdf_dense_sample on the table: a cell touches
+ * 1, 2, 4 or 8 blocks, each probed once; a voxel without an entry has weight 0.  The same results
+ * as on the densified volume.  TSDF_E_ARG also for a shard (n_shards > 1). */
+int tsdf_hash_track_sdf(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width,
+                        const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
+                        double out_pose[16], tsdf_track_info_t* info, double* trajectory, int flags);
+int tsdf_hash_sdf_linearize(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width,
+                            const double K[9], const double rel_pose[16], const double pose_guess[16],
+                            const tsdf_icp_params_t* params, double sums[28], int64_t counts[2],
+                            uint8_t* code, float* residual, int flags);
+int tsdf_hash_sample(tsdf_hash_t* h, const double* points, int64_t n, float* sdf, float* grad,
+                     uint8_t* code, int flags);
 /* HIP-event times, in milliseconds, of the calling thread's last track on a handle with profiling
- * on: ms[0] the raycast, ms[1] the setup (frame copy, state, pixel tables), ms[2] and ms[3] the
+ * on: ms[0] the raycast (0 for tsdf_*_track_sdf, which queues none), ms[1] the setup (frame copy, state, pixel tables), ms[2] and ms[3] the
  * linearise and the finish launches summed over the iterations run, ms[4] the launches that
  * fell through after a status was set.  -1 before any such call. */
 int tsdf_track_last_ms(double ms[5], int* iterations);

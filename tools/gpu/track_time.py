@@ -19,7 +19,12 @@ are compared with the trajectory's own.  Prints one JSON object.
 --color measures the photometric term (tsdf_*_track_rgbd) instead of the strides: per
 handle the geometric track and the RGB-D track at stride 1, alternately configured in the same run
 on the same build, the frames' RGB images resident on the device; the RGB-D figures add the prep
-launch (tsdf_track_last_prep_ms), which is part of the total."""
+launch (tsdf_track_last_prep_ms), which is part of the total.
+
+--sdf measures the point-to-SDF alignment (tsdf_*_track_sdf) against the ICP: per handle
+and stride the ICP track and the SDF track, alternately configured in the same run on the same build
+(icp, sdf, icp_again, sdf_again at stride 1, then icp and sdf at stride 2).  An SDF track queues no
+raycast, so its raycast figure is 0 and "raycast alone" does not apply to it."""
 import argparse
 import contextlib
 import ctypes
@@ -49,9 +54,9 @@ def summary(v, scale=1e3, digits=1):
             "max": round(scale * max(v), digits)}
 
 
-def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, rgb=None):
+def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, rgb=None, method="icp"):
     """rgb: the frames' RGB8 images on the device -- then the RGB-D track is timed (the prep launch
-    as a sixth figure), else the geometric one (prep 0)."""
+    as a sixth figure), else the geometric one (prep 0).  method "sdf": the SDF track."""
     Kp = _ffi.ptr(_ffi.f64(K, 9))
     prm = tracking.icp_params(stride=stride)
     cprm, cinfo = tracking.color_params(), _ffi.TrackColorInfo()
@@ -61,7 +66,9 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, 
         head = (obj._h, depth[f].data_ptr(), _ffi.DEPTH_U16_MM)
         cam = (HW[0], HW[1], Kp, _ffi.ptr(_ffi.f64(poses[f - 1], 16)), ctypes.byref(prm))
         prep = ctypes.c_double(0.0)
-        if rgb is None:
+        if method == "sdf":
+            _ffi.call(f"tsdf_{name}_track_sdf", *head, *cam, _ffi.ptr(out), ctypes.byref(info), None, _ffi.DEVICE_PTRS)
+        elif rgb is None:
             _ffi.call(f"tsdf_{name}_track", *head, *cam, 0.0, z_far, VOXEL, _ffi.ptr(out), ctypes.byref(info), None,
                       _ffi.DEVICE_PTRS)
         else:
@@ -109,13 +116,14 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, 
         s = pose_error(poses[f - 1], poses[f])
         err_t.append(e[0]); err_r.append(e[1]); start_t.append(s[0]); start_r.append(s[1])  # noqa: E702
     alone, alone_live = [], []
-    for f in frames:
+    for f in frames if method != "sdf" else ():
         alone.append(float(np.median([cast(f, 0)[1] for _ in range(REPS)])))
         alone_live.append(float(np.median([sum(cast(f, _ffi.RAY_REFLAG)) for _ in range(REPS)])))
     res = {k + "_us": summary(v) for k, v in cols.items() if k != "raycast_share"}
     res["raycast_share_of_total"] = summary(cols["raycast_share"], 1.0, 3)
-    res["raycast_alone_us"] = summary(alone)
-    res["raycast_alone_with_live_pass_us"] = summary(alone_live)
+    if method != "sdf":
+        res["raycast_alone_us"] = summary(alone)
+        res["raycast_alone_with_live_pass_us"] = summary(alone_live)
     res["iterations"] = {"median": float(np.median(iters)), "min": min(iters), "max": max(iters)}
     res["status"] = {s: status.count(s) for s in sorted(set(status))}
     res["inliers"] = {"median": float(np.median(inliers)), "min": int(min(inliers)), "max": int(max(inliers))}
@@ -130,6 +138,7 @@ def time_config(obj, name, K, poses, depth, stride, z_far, maps, preheat_s=0.3, 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--color", action="store_true", help="geometric against RGB-D track at stride 1 (see above)")
+    ap.add_argument("--sdf", action="store_true", help="ICP against SDF track at stride 1 and 2 (see above)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     poses = scene.trajectory(FRAMES, seed=0, radius_frac=scene.BENCH_RING)
@@ -157,8 +166,12 @@ def main():
         obj.set_profiling(True)
         configs = ([("stride1", 1, None), ("stride2", 2, None)] if not args.color else
                    [("geometry", 1, None), ("rgbd", 1, rgb), ("geometry_again", 1, None), ("rgbd_again", 1, rgb)])
+        if args.sdf:
+            configs = [("icp_stride1", 1, None), ("sdf_stride1", 1, None), ("icp_stride1_again", 1, None),
+                       ("sdf_stride1_again", 1, None), ("icp_stride2", 2, None), ("sdf_stride2", 2, None)]
         for label, stride, images in configs:
-            r = time_config(obj, name, K, poses, depth, stride, z_far, maps, rgb=images)
+            r = time_config(obj, name, K, poses, depth, stride, z_far, maps, rgb=images,
+                            method="sdf" if label.startswith("sdf") else "icp")
             res[f"{name}_{label}"] = r
             print(name, label, json.dumps(r), file=sys.stderr, flush=True)
         obj.close()

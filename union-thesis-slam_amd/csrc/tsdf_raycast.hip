@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "tsdf_cell.h"
 #include "tsdf_host.h"
 
 using namespace tsdf;
@@ -51,16 +52,7 @@ struct RayArgs {
     unsigned char* colors;
 };
 
-__device__ inline float lerp(float a, float b, float t) { return a + t * (b - a); }
-
-// floor(q) as an int, safe for any q (NaN and huge values land far outside every volume)
-__device__ inline int floor_i(float q) { return (int)floorf(fminf(fmaxf(q, -1.0e9f), 1.0e9f)); }
-
-// ---- dense: brick b = (bx*nb1 + by)*nb2 + bz, local voxel (x*8 + y)*8 + z ---------------------
-__device__ inline size_t dense_index(const Vol& v, int x, int y, int z) {
-    const size_t b = ((size_t)(x >> 3) * v.nb[1] + (y >> 3)) * v.nb[2] + (z >> 3);
-    return b * kBrickVox + (size_t)(((x & 7) * 8 + (y & 7)) * 8 + (z & 7));
-}
+// (lerp, floor_i, dense_index, trilinear and the gradient: tsdf_cell.h, shared with the tracker)
 
 // ---- hash: the pool blocks of a 2x2x2 block neighbourhood, per ray, in LDS --------------------
 // nb[slot * kRayWG] (slot = ox*4 + oy*2 + oz) is the pool block of block A + (ox, oy, oz), or -1.
@@ -97,17 +89,7 @@ __device__ inline void hash_voxel(const RayArgs& a, const Hood& h, int x, int y,
     *t = COLOR ? 0.0f : 1.0f;
     *w = 0.0f;
     if ((unsigned)s > 7u) return;  // (never: hood_cover ran for this cell)
-    const int blk = h.nb[s * kRayWG];
-    if (blk < 0) return;
-    const unsigned long long word = coh_load(&a.t.occ[(size_t)blk * 8 + (z & 7)]);
-    if (!((word >> ((x & 7) * 8 + (y & 7))) & 1ull)) return;
-    const size_t j = (size_t)blk * kBrickVox + (size_t)(((x & 7) * 8 + (y & 7)) * 8 + (z & 7));
-    if (COLOR) {
-        *t = a.pool.color[j];
-    } else {
-        *t = a.pool.tsdf[j];
-        *w = a.pool.weight[j];
-    }
+    hash_block_voxel<COLOR>(a.t, a.pool, h.nb[s * kRayWG], x, y, z, t, w);
 }
 
 // The 8 corner values of the cell at local index l (c[dx*4 + dy*2 + dz]); false: not valid.
@@ -131,12 +113,6 @@ __device__ inline bool load_cell(const RayArgs& a, Hood& h, const int l[3], cons
         valid = valid && w > 0.0f;
     }
     return valid;
-}
-
-__device__ inline float trilinear(const float c[8], const float t[3]) {
-    const float c00 = lerp(c[0], c[1], t[2]), c01 = lerp(c[2], c[3], t[2]);
-    const float c10 = lerp(c[4], c[5], t[2]), c11 = lerp(c[6], c[7], t[2]);
-    return lerp(lerp(c00, c01, t[1]), lerp(c10, c11, t[1]), t[0]);
 }
 
 struct Ray {
@@ -300,12 +276,9 @@ __global__ __launch_bounds__(kRayWG) void k_raycast(RayArgs a) {
                 rgb[1] = (unsigned char)(int)floorf(cg);
                 rgb[2] = (unsigned char)(int)floorf(cb);
                 if (a.normals && load_cell<HASH>(a, h, l, r.qd, cs)) {
-                    const float gx = lerp(lerp(cs[4] - cs[0], cs[5] - cs[1], ts[2]),
-                                          lerp(cs[6] - cs[2], cs[7] - cs[3], ts[2]), ts[1]);
-                    const float gy = lerp(lerp(cs[2] - cs[0], cs[3] - cs[1], ts[2]),
-                                          lerp(cs[6] - cs[4], cs[7] - cs[5], ts[2]), ts[0]);
-                    const float gz = lerp(lerp(cs[1] - cs[0], cs[3] - cs[2], ts[1]),
-                                          lerp(cs[5] - cs[4], cs[7] - cs[6], ts[1]), ts[0]);
+                    float g[3];
+                    cell_gradient(cs, ts, g);
+                    const float gx = g[0], gy = g[1], gz = g[2];
                     const float len = __fsqrt_rn((gx * gx + gy * gy) + gz * gz);
                     if (len > 0.0f) {
                         nrm[0] = gx / len;

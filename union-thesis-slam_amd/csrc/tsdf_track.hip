@@ -29,6 +29,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "tsdf_cell.h"
 #include "tsdf_host.h"
 
 using namespace tsdf;
@@ -180,6 +181,65 @@ __device__ inline float bilerp(float t00, float t01, float t10, float t11, float
     return lerpf(lerpf(t00, t01, tx), lerpf(t10, t11, tx), ty);
 }
 
+// ---- what the linearise kernels share (k_icp_linearize, k_sdf_linearize) ---------------------------
+// One inlier row into a lane's sums s[BASE .. BASE + 27]: the 21 upper-triangle products of J, the 6
+// of J r, and r r, each an exact f64 product of two f32 values.
+template <int BASE, int N>
+__device__ inline void icp_add_row(double (&s)[N], const float (&J)[6], float r) {
+    int k = BASE;
+#pragma unroll
+    for (int x = 0; x < 6; ++x)
+#pragma unroll
+        for (int y = x; y < 6; ++y) s[k++] += (double)J[x] * (double)J[y];
+#pragma unroll
+    for (int x = 0; x < 6; ++x) s[BASE + 21 + x] += (double)J[x] * (double)r;
+    s[BASE + 27] += (double)r * (double)r;
+}
+
+// The lanes' sums and counts to one partial record per workgroup (kIcpRec doubles per term; COLOR:
+// two terms), in an order the launch shape alone fixes.
+template <bool COLOR>
+__device__ inline void icp_reduce(double (&s)[COLOR ? 56 : 28], unsigned n_in, unsigned n_cand, [[maybe_unused]] unsigned c_in,
+                                  [[maybe_unused]] unsigned c_cand, double* partial) {
+    constexpr int kSums = COLOR ? 56 : 28;
+    constexpr int kRec = COLOR ? 2 * kIcpRec : kIcpRec;
+    // the wave: a butterfly (every lane ends with the same sum, formed in the same order)
+#pragma unroll
+    for (int i = 0; i < kSums; ++i)
+        for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+    for (int o = 32; o > 0; o >>= 1) {
+        n_in += __shfl_xor(n_in, o);
+        n_cand += __shfl_xor(n_cand, o);
+        if constexpr (COLOR) {
+            c_in += __shfl_xor(c_in, o);
+            c_cand += __shfl_xor(c_cand, o);
+        }
+    }
+    // the workgroup: through LDS, waves added in wave order
+    __shared__ double sh[kIcpWG / 64][kRec];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 28; ++i) sh[wave][i] = s[i];
+        sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
+        sh[wave][29] = (double)n_cand;
+        sh[wave][30] = sh[wave][31] = 0.0;
+        if constexpr (COLOR) {
+#pragma unroll
+            for (int i = 0; i < 28; ++i) sh[wave][kIcpRec + i] = s[28 + i];
+            sh[wave][kIcpRec + 28] = (double)c_in;
+            sh[wave][kIcpRec + 29] = (double)c_cand;
+            sh[wave][kIcpRec + 30] = sh[wave][kIcpRec + 31] = 0.0;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < kRec) {
+        double t = sh[0][threadIdx.x];
+        for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * kRec + threadIdx.x] = t;
+    }
+}
+
 // ---- the iteration's two kernels ----------------------------------------------
 // COLOR = false is the geometric track.  COLOR = true adds, in the same pass over the frame, the
 // photometric term: the frame's depth is read once, p and the projection are shared, and the
@@ -193,8 +253,7 @@ __device__ inline float bilerp(float t00, float t01, float t10, float t11, float
 //   5 inlier
 template <int DK, bool COLOR>
 __global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
-    constexpr int kSums = COLOR ? 56 : 28;               // per lane: 0..27 geometric, 28..55 colour
-    constexpr int kRec = COLOR ? 2 * kIcpRec : kIcpRec;  // doubles per partial record
+    constexpr int kSums = COLOR ? 56 : 28;  // per lane: 0..27 geometric, 28..55 colour
     if (a.st->status != kIcpRunning) return;  // a status is set: the queued launches fall through
     float M[12];
     for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
@@ -305,14 +364,7 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
         if (code >= 2) ++n_cand;
         if (code == 6) {
             ++n_in;
-            int k = 0;
-#pragma unroll
-            for (int x = 0; x < 6; ++x)
-#pragma unroll
-                for (int y = x; y < 6; ++y) s[k++] += (double)J[x] * (double)J[y];
-#pragma unroll
-            for (int x = 0; x < 6; ++x) s[21 + x] += (double)J[x] * (double)r;
-            s[27] += (double)r * (double)r;
+            icp_add_row<0>(s, J, r);
         }
         if (a.code) a.code[pf] = (unsigned char)code;
         if (a.resid) a.resid[pf] = r;
@@ -320,55 +372,166 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
             if (cc >= 2) ++c_cand;
             if (cc == 5) {
                 ++c_in;
-                int k = 28;
-#pragma unroll
-                for (int x = 0; x < 6; ++x)
-#pragma unroll
-                    for (int y = x; y < 6; ++y) s[k++] += (double)Jc[x] * (double)Jc[y];
-#pragma unroll
-                for (int x = 0; x < 6; ++x) s[49 + x] += (double)Jc[x] * (double)rc;
-                s[55] += (double)rc * (double)rc;
+                icp_add_row<28>(s, Jc, rc);
             }
             if (a.ccode) a.ccode[pf] = (unsigned char)cc;
             if (a.cresid) a.cresid[pf] = rc;
         }
     }
 
-    // the wave: a butterfly (every lane ends with the same sum, formed in the same order)
+    icp_reduce<COLOR>(s, n_in, n_cand, c_in, c_cand, a.partial);
+}
+
+// ---- point-to-SDF alignment -------------------------------------------------------
+// The volume is a signed distance field, so a frame can be aligned to it directly: minimise the sum
+// of sdf(G M p)^2 over the frame's points, with the trilinear interpolant of the stored tsdf and its
+// gradient (tsdf_cell.h, the raycast's own arithmetic).  No raycast, no model maps, no frame normals.
+// The row has the ICP's form (n the metric gradient in the guess camera's frame, r = -sdf), so the
+// sums, the finish, the records and the host path are the ICP's.  Restated by tests/sdf_ref.py.  Codes:
+//   0 not sampled / no depth     2 the cell is not inside the volume     3 a corner has weight <= 0
+//   4 a corner lies on the truncated plateau (|tsdf| >= 1)     5 |r| > dist_max or a zero gradient
+//   6 inlier
+struct SdfArgs {
+    Vol v;
+    Pool pool;
+    Table t;             // hash only
+    int hash;
+    float Qr[9], Qo[3];  // the guess camera's frame to index space: R_G / vs, (t_G - origin) / vs
+    float sc, trunc;     // trunc / vs (tsdf per voxel to metres per metre), trunc
+};
+
+// The cell at local index l (corners l + {0,1}^3, c[dx*4 + dy*2 + dz]) and its code: 2, 3, 4 or 6; c
+// is filled for 4 and 6.  Dense: the 16 gathers are issued together.  Hash: a cell touches 1, 2, 4
+// or 8 blocks ((l & 7) == 7 on an axis crosses to the next); each distinct block is probed once.
+template <bool HASH>
+__device__ inline int sdf_cell(const SdfArgs& x, const int l[3], float c[8]) {
+    for (int d = 0; d < 3; ++d)
+        if (l[d] < 0 || l[d] > x.v.dims[d] - 2) return 2;
+    float w[8];
+    if (HASH) {
+        const bool cr[3] = {(l[0] & 7) == 7, (l[1] & 7) == 7, (l[2] & 7) == 7};
+        int blk[8];  // the pool block of corner s
 #pragma unroll
-    for (int i = 0; i < kSums; ++i)
-        for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
-    for (int o = 32; o > 0; o >>= 1) {
-        n_in += __shfl_xor(n_in, o);
-        n_cand += __shfl_xor(n_cand, o);
-        if constexpr (COLOR) {
-            c_in += __shfl_xor(c_in, o);
-            c_cand += __shfl_xor(c_cand, o);
+        for (int s = 0; s < 8; ++s) {
+            const int ox = s >> 2, oy = (s >> 1) & 1, oz = s & 1;
+            if (ox && !cr[0]) blk[s] = blk[s & 3];
+            else if (oy && !cr[1]) blk[s] = blk[s & 5];
+            else if (oz && !cr[2]) blk[s] = blk[s & 6];
+            else {
+                const int bx = (l[0] >> 3) + ox, by = (l[1] >> 3) + oy, bz = (l[2] >> 3) + oz;
+                blk[s] = bx < x.v.nb[0] && by < x.v.nb[1] && bz < x.v.nb[2] ? hash_find(x.t, bx, by, bz, x.t.max_blocks) : -1;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+            hash_block_voxel<false>(x.t, x.pool, blk[s], l[0] + (s >> 2), l[1] + ((s >> 1) & 1), l[2] + (s & 1), &c[s], &w[s]);
+    } else {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const size_t j = dense_index(x.v, l[0] + (s >> 2), l[1] + ((s >> 1) & 1), l[2] + (s & 1));
+            c[s] = x.pool.tsdf[j];
+            w[s] = x.pool.weight[j];
         }
     }
-    // the workgroup: through LDS, waves added in wave order
-    __shared__ double sh[kIcpWG / 64][kRec];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
+    bool seen = true, flat = false;
 #pragma unroll
-        for (int i = 0; i < 28; ++i) sh[wave][i] = s[i];
-        sh[wave][28] = (double)n_in;  // (counts < 2^28: exact)
-        sh[wave][29] = (double)n_cand;
-        sh[wave][30] = sh[wave][31] = 0.0;
-        if constexpr (COLOR) {
+    for (int s = 0; s < 8; ++s) {
+        seen = seen && w[s] > 0.0f;
+        flat = flat || fabsf(c[s]) >= 1.0f;
+    }
+    return !seen ? 3 : flat ? 4 : 6;
+}
+
+// One lane per sampled pixel over k_icp_linearize's launch shape, feeding k_icp_finish<false>.
+template <int DK, bool HASH>
+__global__ __launch_bounds__(kIcpWG) void k_sdf_linearize(IcpArgs a, SdfArgs x) {
+    if (a.st->status != kIcpRunning) return;  // a status is set: the queued launches fall through
+    float M[12];
+    for (int i = 0; i < 12; ++i) M[i] = (float)a.st->M[i];
+
+    double s[28];
 #pragma unroll
-            for (int i = 0; i < 28; ++i) sh[wave][kIcpRec + i] = s[28 + i];
-            sh[wave][kIcpRec + 28] = (double)c_in;
-            sh[wave][kIcpRec + 29] = (double)c_cand;
-            sh[wave][kIcpRec + 30] = sh[wave][kIcpRec + 31] = 0.0;
+    for (int i = 0; i < 28; ++i) s[i] = 0.0;
+    unsigned n_in = 0, n_cand = 0;
+
+    const long long n = (long long)a.su * a.sv;
+    for (long long i = (long long)blockIdx.x * kIcpWG + threadIdx.x; i < n; i += (long long)gridDim.x * kIcpWG) {
+        const int u = (int)(i % a.su) * a.stride, v = (int)(i / a.su) * a.stride;
+        const size_t pf = (size_t)v * a.Wf + u;
+        int code = 0;
+        float r = 0.0f, J[6];
+        const float d = depth_at<DK>(a, u, v);
+        if (good_depth(d)) {
+            const float V[3] = {a.xf[u] * d, a.yf[v] * d, d};
+            float p[3], t[3], c[8];
+            int l[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[k] = ((M[4 * k] * V[0] + M[4 * k + 1] * V[1]) + M[4 * k + 2] * V[2]) + M[4 * k + 3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float q = ((x.Qr[3 * k] * p[0] + x.Qr[3 * k + 1] * p[1]) + x.Qr[3 * k + 2] * p[2]) + x.Qo[k];
+                const int i0 = floor_i(q);
+                t[k] = q - (float)i0;
+                l[k] = i0 - x.v.off[k];
+            }
+            code = sdf_cell<HASH>(x, l, c);
+            if (code == 6) {
+                float g[3];
+                const float f = trilinear(c, t);
+                cell_gradient(c, t, g);
+                const float res = -(x.trunc * f);
+                if (fabsf(res) > a.dist_max || (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f)) {
+                    code = 5;
+                } else {
+                    float nn[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) nn[k] = x.sc * ((a.Rm[k] * g[0] + a.Rm[3 + k] * g[1]) + a.Rm[6 + k] * g[2]);
+                    r = res;
+                    J[0] = p[1] * nn[2] - p[2] * nn[1];
+                    J[1] = p[2] * nn[0] - p[0] * nn[2];
+                    J[2] = p[0] * nn[1] - p[1] * nn[0];
+                    J[3] = nn[0];
+                    J[4] = nn[1];
+                    J[5] = nn[2];
+                }
+            }
         }
+        if (code >= 2) ++n_cand;
+        if (code == 6) {
+            ++n_in;
+            icp_add_row<0>(s, J, r);
+        }
+        if (a.code) a.code[pf] = (unsigned char)code;
+        if (a.resid) a.resid[pf] = r;
     }
-    __syncthreads();
-    if (threadIdx.x < kRec) {
-        double t = sh[0][threadIdx.x];
-        for (int w = 1; w < kIcpWG / 64; ++w) t += sh[w][threadIdx.x];
-        a.partial[(size_t)blockIdx.x * kRec + threadIdx.x] = t;
+    icp_reduce<false>(s, n_in, n_cand, 0u, 0u, a.partial);
+}
+
+// tsdf_*_sample: the same cell at n world points.
+template <bool HASH>
+__global__ __launch_bounds__(256) void k_sdf_sample(SdfArgs x, const double* P, long long n, float* sdf, float* grad,
+                                                    unsigned char* code) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float t[3], c[8];
+    int l[3];
+    for (int k = 0; k < 3; ++k) {
+        const float q = (float)((P[3 * i + k] - (double)x.v.origin[k]) / x.v.vs);
+        const int i0 = floor_i(q);
+        t[k] = q - (float)i0;
+        l[k] = i0 - x.v.off[k];
     }
+    const int cd = sdf_cell<HASH>(x, l, c);
+    float f = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
+    if (cd >= 4) {
+        f = x.trunc * trilinear(c, t);
+        cell_gradient(c, t, g);
+        for (int k = 0; k < 3; ++k) g[k] = x.sc * g[k];
+    }
+    if (sdf) sdf[i] = f;
+    if (grad)
+        for (int k = 0; k < 3; ++k) grad[3 * i + k] = g[k];
+    if (code) code[i] = (unsigned char)cd;
 }
 
 struct FinishArgs {
@@ -592,6 +755,33 @@ struct Images {
     float* cresid;
 };
 
+// The volume's side of an SDF linearisation at pose_guess (null: tsdf_*_sample, which needs none):
+// f64, each value rounded to f32 once.
+void sdf_volume(const RaySource& S, const double* pose_guess, SdfArgs* x) {
+    const Base& B = *S.b;
+    *x = SdfArgs{};
+    x->v = B.vol;
+    x->pool = B.pool;
+    if (S.table) x->t = *S.table;
+    x->hash = S.table ? 1 : 0;
+    for (int r = 0; r < 3 && pose_guess; ++r) {
+        for (int k = 0; k < 3; ++k) x->Qr[3 * r + k] = (float)(pose_guess[4 * r + k] / B.vol.vs);
+        x->Qo[r] = (float)((pose_guess[4 * r + 3] - (double)B.vol.origin[r]) / B.vol.vs);
+    }
+    x->sc = (float)(B.vol.trunc / B.vol.vs);
+    x->trunc = (float)B.vol.trunc;
+}
+
+// The tracking buffers of a handle (created by its first track), on the handle's stream.
+IcpCtx& handle_ctx(Base& B) {
+    if (!B.icp) {
+        B.icp = new IcpCtx();
+        B.icp->device = B.device;
+        B.icp->stream = B.stream;
+    }
+    return *B.icp;
+}
+
 unsigned linearize_grid(const IcpArgs& a, int n_cu) {
     const long long n = (long long)a.su * a.sv;
     return (unsigned)std::max(1ll, std::min<long long>((n + kIcpWG - 1) / kIcpWG, (long long)std::max(n_cu, 1) * 4));
@@ -667,14 +857,21 @@ int prepare(IcpCtx& c, const Cameras& cam, const tsdf_icp_params_t& p, int dk, i
 }
 
 // One iteration: the linearise instance of the depth kind and of whether prepare() saw a colour
-// image, then the finish of the same kind.
-int launch_iteration(IcpCtx& c, const IcpArgs& a, unsigned grid, IcpRecord* rec, int solve, int last,
+// image -- or, with x, the SDF linearise of the depth kind and of the handle's kind --, then the
+// finish of the same kind.
+int launch_iteration(IcpCtx& c, const IcpArgs& a, const SdfArgs* x, unsigned grid, IcpRecord* rec, int solve, int last,
                      const tsdf_icp_params_t& p, const tsdf_icp_color_params_t* q, hipEvent_t ev_mid = nullptr,
                      hipEvent_t ev_end = nullptr) {
     const bool u16 = a.dk == TSDF_DEPTH_U16_MM, rgbd = a.fi != nullptr;
-    auto lin = rgbd ? (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, true> : k_icp_linearize<TSDF_DEPTH_F64_M, true>)
-                    : (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, false> : k_icp_linearize<TSDF_DEPTH_F64_M, false>);
-    hipLaunchKernelGGL(lin, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
+    if (x) {
+        auto lin = x->hash ? (u16 ? k_sdf_linearize<TSDF_DEPTH_U16_MM, true> : k_sdf_linearize<TSDF_DEPTH_F64_M, true>)
+                           : (u16 ? k_sdf_linearize<TSDF_DEPTH_U16_MM, false> : k_sdf_linearize<TSDF_DEPTH_F64_M, false>);
+        hipLaunchKernelGGL(lin, dim3(grid), dim3(kIcpWG), 0, c.stream, a, *x);
+    } else {
+        auto lin = rgbd ? (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, true> : k_icp_linearize<TSDF_DEPTH_F64_M, true>)
+                        : (u16 ? k_icp_linearize<TSDF_DEPTH_U16_MM, false> : k_icp_linearize<TSDF_DEPTH_F64_M, false>);
+        hipLaunchKernelGGL(lin, dim3(grid), dim3(kIcpWG), 0, c.stream, a);
+    }
     TSDF_HIP(hipGetLastError());
     if (ev_mid) TSDF_HIP(hipEventRecord(ev_mid, c.stream));
     FinishArgs f{};
@@ -707,11 +904,13 @@ std::mutex g_dev_mu;
 thread_local double g_track_ms[6] = {-1.0, -1.0, -1.0, -1.0, -1.0, 0.0};
 thread_local double g_track_prep_ms = -1.0;  // the prep launch of its last RGB-D track
 
-// The four handle entry points.  rgbd: the raycast also writes the model's colour map, one prep
-// launch, and the colour instances of the two kernels; else color, q and cinfo are null.
+// The six handle entry points.  rgbd: the raycast also writes the model's colour map, one prep
+// launch, and the colour instances of the two kernels; else color, q and cinfo are null.  sdf (never
+// with rgbd): point-to-SDF alignment on the volume itself (§7g) -- no raycast (cast is null and the
+// z range unused), no model maps; everything else is the same path.
 int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const double*, double, double, double, float*,
                                           float*, uint8_t*, int),
-          void* handle, bool rgbd, const void* depth, int dk, const uint8_t* color, int H, int W, const double* K,
+          void* handle, bool rgbd, bool sdf, const void* depth, int dk, const uint8_t* color, int H, int W, const double* K,
           const double* pose_guess, const tsdf_icp_params_t* p, const tsdf_icp_color_params_t* q, double zn, double zf,
           double zs, double* out_pose, tsdf_track_info_t* info, tsdf_track_color_info_t* cinfo, double* trajectory,
           int flags) {
@@ -726,16 +925,13 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
         return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", H, W);
     TSDF_TRY(check_params(p));
     if (rgbd) TSDF_TRY(check_color_params(q));
-    if (!B.icp) {
-        B.icp = new IcpCtx();
-        B.icp->device = B.device;
-        B.icp->stream = B.stream;
-    }
-    IcpCtx& c = *B.icp;
+    IcpCtx& c = handle_ctx(B);
     const size_t px = (size_t)H * W;
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
-    TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
-    TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
+    if (!sdf) {
+        TSDF_TRY(ensure(c, kBufModelD, px * sizeof(float)));
+        TSDF_TRY(ensure(c, kBufModelN, px * 3 * sizeof(float)));
+    }
     if (rgbd) TSDF_TRY(ensure(c, kBufModelC, px * 3));
     TSDF_TRY(ensure(c, kBufState, state_bytes(p->max_iter)));
     Images im{};
@@ -749,8 +945,8 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
             im.rgb = (const unsigned char*)c.buf[kBufRgb];
         }
     }
-    im.dm = (const float*)c.buf[kBufModelD];
-    im.nm = (const float*)c.buf[kBufModelN];
+    im.dm = sdf ? nullptr : (const float*)c.buf[kBufModelD];
+    im.nm = sdf ? nullptr : (const float*)c.buf[kBufModelN];
     im.mc = rgbd ? (const unsigned char*)c.buf[kBufModelC] : nullptr;
     // profiling on: events around the raycast, the setup, the prep of an RGB-D track and every launch
     // of the iterations
@@ -768,8 +964,9 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     if (timed) TSDF_HIP(hipEventRecord(ev[0], c.stream));
     // the model maps: the handle's own raycast at pose_guess (it runs the deferred frames first and
     // refuses what a raycast refuses)
-    TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN],
-                  rgbd ? (uint8_t*)c.buf[kBufModelC] : nullptr, TSDF_DEVICE_PTRS | TSDF_ASYNC));
+    if (!sdf)
+        TSDF_TRY(cast(handle, H, W, K, pose_guess, zn, zf, zs, (float*)c.buf[kBufModelD], (float*)c.buf[kBufModelN],
+                      rgbd ? (uint8_t*)c.buf[kBufModelC] : nullptr, TSDF_DEVICE_PTRS | TSDF_ASYNC));
     if (timed) TSDF_HIP(hipEventRecord(ev[1], c.stream));
     if (!dev) {
         TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], depth, frame_bytes_depth(dk, H, W), hipMemcpyHostToDevice, c.stream));
@@ -779,13 +976,15 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
     IcpRecord* rec = (IcpRecord*)(sb + kRecOff);
     hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, c.stream, (IcpState*)(sb + kStateOff), (const double*)nullptr);
     TSDF_HIP(hipGetLastError());
-    Cameras cam{H, W, H, W, K, K, pose_guess};
+    Cameras cam{H, W, sdf ? 0 : H, sdf ? 0 : W, K, K, pose_guess};  // (SDF: no model camera; Rm is R_G either way)
     IcpArgs a;
+    SdfArgs sx;
+    if (sdf) sdf_volume(S, pose_guess, &sx);
     unsigned grid;
     TSDF_TRY(prepare(c, cam, *p, dk, flags, im, q, B.n_cu, &a, &grid, timed && rgbd ? ev[2] : nullptr));
     if (timed) TSDF_HIP(hipEventRecord(ev[2 + off], c.stream));
     for (int it = 0; it < p->max_iter; ++it)
-        TSDF_TRY(launch_iteration(c, a, grid, rec + it, 1, it == p->max_iter - 1, *p, q,
+        TSDF_TRY(launch_iteration(c, a, sdf ? &sx : nullptr, grid, rec + it, 1, it == p->max_iter - 1, *p, q,
                                   timed ? ev[3 + off + 2 * it] : nullptr, timed ? ev[4 + off + 2 * it] : nullptr));
     // one synchronisation, one copy back
     std::vector<char> host(state_bytes(p->max_iter));
@@ -800,7 +999,7 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
         for (size_t i = 0; i + 1 < ev.size(); ++i) {
             float x = 0.0f;
             TSDF_HIP(hipEventElapsedTime(&x, ev[i], ev[i + 1]));
-            if (i < 2) ms[i] += x;
+            if (i < 2) ms[i] += sdf && i == 0 ? 0.0f : x;  // (no raycast was queued between ev[0] and ev[1])
             else if (i < 2 + off) prep += x;
             else ms[(int)(i - 2 - off) / 2 >= iters ? 4 : 2 + (int)(i - 2 - off) % 2] += x;
         }
@@ -878,28 +1077,35 @@ int device_context(int device, IcpCtx** out, int* n_cu) {
     return TSDF_OK;
 }
 
-// The two handle-less entry points: one linearisation at rel_pose, no solve.  rgbd: sums[56] and
-// counts[4], else sums[28] and counts[2], and color, model_colors, q and the colour maps are null.
-int linearize_once(bool rgbd, int device, const void* depth, int dk, const uint8_t* color, int Hf, int Wf, const double* Kf,
+// The two handle-less entry points and the two SDF ones: one linearisation at rel_pose, no solve.
+// rgbd: sums[56] and counts[4], else sums[28] and counts[2], and color, model_colors, q and the colour
+// maps are null.  S (never with rgbd): the SDF linearisation on that handle, with its buffers and on
+// its stream; the model maps and the model camera are null / 0 and model_pose is the guess.
+int linearize_once(const RaySource* S, bool rgbd, int device, const void* depth, int dk, const uint8_t* color, int Hf, int Wf, const double* Kf,
                    const double* rel_pose, const float* model_depth, const float* model_normals, const uint8_t* model_colors,
                    int Hm, int Wm, const double* Km, const double* model_pose, const tsdf_icp_params_t* params,
                    const tsdf_icp_color_params_t* q, double* sums, int64_t* counts, uint8_t* code, float* residual,
                    uint8_t* color_code, float* color_residual, int flags) {
     if (!depth) return set_error(TSDF_E_ARG, "null depth pointer");
     if (rgbd && !color) return set_error(TSDF_E_ARG, "null color image pointer");
-    if (!model_depth || !model_normals || (rgbd && !model_colors)) return set_error(TSDF_E_ARG, "null model map pointer");
+    if (!S && (!model_depth || !model_normals || (rgbd && !model_colors))) return set_error(TSDF_E_ARG, "null model map pointer");
     if (!Kf || !Km || !rel_pose || !model_pose) return set_error(TSDF_E_ARG, "null camera pointer");
     if (!sums || !counts) return set_error(TSDF_E_ARG, "null sums / counts pointer");
     if (dk != TSDF_DEPTH_U16_MM && dk != TSDF_DEPTH_F64_M) return set_error(TSDF_E_ARG, "bad depth_kind %d", dk);
     if (bad_size(Hf, Wf)) return set_error(TSDF_E_ARG, "bad frame image size %dx%d", Hf, Wf);
-    if (bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
+    if (!S && bad_size(Hm, Wm)) return set_error(TSDF_E_ARG, "bad model image size %dx%d", Hm, Wm);
     if (rgbd && (Hm < 4 || Wm < 4))
         return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", Hm, Wm);
     TSDF_TRY(check_params(params));
     if (rgbd) TSDF_TRY(check_color_params(q));
     IcpCtx* cp;
     int n_cu;
-    TSDF_TRY(device_context(device, &cp, &n_cu));
+    if (S) {
+        cp = &handle_ctx(*S->b);
+        n_cu = S->b->n_cu;
+    } else {
+        TSDF_TRY(device_context(device, &cp, &n_cu));
+    }
     IcpCtx& c = *cp;
     std::lock_guard<std::mutex> lk(c.mu);  // one call at a time per device context
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
@@ -941,9 +1147,11 @@ int linearize_once(bool rgbd, int device, const void* depth, int dk, const uint8
                     (const unsigned char*)din[4], (unsigned char*)dout[0], (float*)dout[1], (unsigned char*)dout[2],
                     (float*)dout[3]};
     IcpArgs a;
+    SdfArgs sx;
+    if (S) sdf_volume(*S, model_pose, &sx);
     unsigned grid;
     TSDF_TRY(prepare(c, cam, *params, dk, flags, im, q, n_cu, &a, &grid));
-    TSDF_TRY(launch_iteration(c, a, grid, (IcpRecord*)(sb + kRecOff), 0, 1, *params, q));
+    TSDF_TRY(launch_iteration(c, a, S ? &sx : nullptr, grid, (IcpRecord*)(sb + kRecOff), 0, 1, *params, q));
     IcpRecord rec;
     TSDF_HIP(hipMemcpyAsync(&rec, sb + kRecOff, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
     if (!dev)
@@ -961,6 +1169,42 @@ int linearize_once(bool rgbd, int device, const void* depth, int dk, const uint8
     return TSDF_OK;
 }
 
+// tsdf_*_sample: the cell of k_sdf_linearize at n world points, through the handle's tracking buffers.
+int sample(const RaySource& S, const double* points, int64_t n, float* sdf, float* grad, uint8_t* code, int flags) {
+    Base& B = *S.b;
+    if (n < 0 || n >= (1ll << 31)) return set_error(TSDF_E_ARG, "bad point count %lld", (long long)n);
+    if (n == 0) return TSDF_OK;
+    if (!points) return set_error(TSDF_E_ARG, "null points pointer");
+    IcpCtx& c = handle_ctx(B);
+    const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    const double* dp = points;
+    void* out[3] = {sdf, grad, code};
+    const int buf[3] = {kBufResid, kBufModelN, kBufCode};
+    const size_t bytes[3] = {(size_t)n * sizeof(float), (size_t)n * 3 * sizeof(float), (size_t)n};
+    void* dout[3] = {sdf, grad, code};
+    if (!dev) {
+        TSDF_TRY(ensure(c, kBufDepth, (size_t)n * 3 * sizeof(double)));
+        TSDF_HIP(hipMemcpyAsync(c.buf[kBufDepth], points, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c.stream));
+        dp = (const double*)c.buf[kBufDepth];
+        for (int i = 0; i < 3; ++i) {
+            if (!out[i]) continue;
+            TSDF_TRY(ensure(c, buf[i], bytes[i]));
+            dout[i] = c.buf[buf[i]];
+        }
+    }
+    SdfArgs sx;
+    sdf_volume(S, nullptr, &sx);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(sx.hash ? k_sdf_sample<true> : k_sdf_sample<false>, dim3(grid), dim3(256), 0, c.stream, sx, dp,
+                       (long long)n, (float*)dout[0], (float*)dout[1], (unsigned char*)dout[2]);
+    TSDF_HIP(hipGetLastError());
+    if (!dev)
+        for (int i = 0; i < 3; ++i)
+            if (out[i]) TSDF_HIP(hipMemcpyAsync(out[i], dout[i], bytes[i], hipMemcpyDeviceToHost, c.stream));
+    TSDF_HIP(hipStreamSynchronize(c.stream));
+    return TSDF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -969,7 +1213,7 @@ int tsdf_icp_linearize(int device, const void* depth, int depth_kind, int Hf, in
                        const double rel_pose[16], const float* model_depth, const float* model_normals, int Hm, int Wm,
                        const double Km[9], const double model_pose[16], const tsdf_icp_params_t* params, double sums[28],
                        int64_t counts[2], uint8_t* code, float* residual, int flags) {
-    return linearize_once(false, device, depth, depth_kind, nullptr, Hf, Wf, Kf, rel_pose, model_depth, model_normals, nullptr,
+    return linearize_once(nullptr, false, device, depth, depth_kind, nullptr, Hf, Wf, Kf, rel_pose, model_depth, model_normals, nullptr,
                           Hm, Wm, Km, model_pose, params, nullptr, sums, counts, code, residual, nullptr, nullptr, flags);
 }
 
@@ -979,7 +1223,7 @@ int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const
                             const double model_pose[16], const tsdf_icp_params_t* params,
                             const tsdf_icp_color_params_t* color_params, double sums[56], int64_t counts[4], uint8_t* code,
                             float* residual, uint8_t* color_code, float* color_residual, int flags) {
-    return linearize_once(true, device, depth, depth_kind, color, Hf, Wf, Kf, rel_pose, model_depth, model_normals,
+    return linearize_once(nullptr, true, device, depth, depth_kind, color, Hf, Wf, Kf, rel_pose, model_depth, model_normals,
                           model_colors, Hm, Wm, Km, model_pose, params, color_params, sums, counts, code, residual, color_code,
                           color_residual, flags);
 }
@@ -990,7 +1234,7 @@ int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int hei
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(dense_ray_source(h, &S));
-    return track(S, cast_dense, h, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
+    return track(S, cast_dense, h, false, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
                  z_far, z_step, out_pose, info, nullptr, trajectory, flags);
 }
 
@@ -1000,7 +1244,7 @@ int tsdf_hash_track(tsdf_hash_t* h, const void* depth, int depth_kind, int heigh
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(hash_ray_source(h, &S));
-    return track(S, cast_hash, h, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
+    return track(S, cast_hash, h, false, false, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, z_near,
                  z_far, z_step, out_pose, info, nullptr, trajectory, flags);
 }
 
@@ -1012,7 +1256,7 @@ int tsdf_dense_track_rgbd(tsdf_dense_t* h, const void* depth, int depth_kind, co
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(dense_ray_source(h, &S));
-    return track(S, cast_dense, h, true, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+    return track(S, cast_dense, h, true, false, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
                  z_far, z_step, out_pose, info, color_info, trajectory, flags);
 }
 
@@ -1024,8 +1268,62 @@ int tsdf_hash_track_rgbd(tsdf_hash_t* h, const void* depth, int depth_kind, cons
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     RaySource S;
     TSDF_TRY(hash_ray_source(h, &S));
-    return track(S, cast_hash, h, true, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
+    return track(S, cast_hash, h, true, false, depth, depth_kind, color, height, width, K, pose_guess, params, color_params, z_near,
                  z_far, z_step, out_pose, info, color_info, trajectory, flags);
+}
+
+int tsdf_dense_track_sdf(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                         const double pose_guess[16], const tsdf_icp_params_t* params, double out_pose[16],
+                         tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return track(S, nullptr, h, false, true, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, 0.0, 0.0,
+                 0.0, out_pose, info, nullptr, trajectory, flags);
+}
+
+int tsdf_hash_track_sdf(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                        const double pose_guess[16], const tsdf_icp_params_t* params, double out_pose[16],
+                        tsdf_track_info_t* info, double* trajectory, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return track(S, nullptr, h, false, true, depth, depth_kind, nullptr, height, width, K, pose_guess, params, nullptr, 0.0, 0.0,
+                 0.0, out_pose, info, nullptr, trajectory, flags);
+}
+
+int tsdf_dense_sdf_linearize(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                             const double rel_pose[16], const double pose_guess[16], const tsdf_icp_params_t* params,
+                             double sums[28], int64_t counts[2], uint8_t* code, float* residual, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return linearize_once(&S, false, 0, depth, depth_kind, nullptr, height, width, K, rel_pose, nullptr, nullptr, nullptr, 0, 0,
+                          K, pose_guess, params, nullptr, sums, counts, code, residual, nullptr, nullptr, flags);
+}
+
+int tsdf_hash_sdf_linearize(tsdf_hash_t* h, const void* depth, int depth_kind, int height, int width, const double K[9],
+                            const double rel_pose[16], const double pose_guess[16], const tsdf_icp_params_t* params,
+                            double sums[28], int64_t counts[2], uint8_t* code, float* residual, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return linearize_once(&S, false, 0, depth, depth_kind, nullptr, height, width, K, rel_pose, nullptr, nullptr, nullptr, 0, 0,
+                          K, pose_guess, params, nullptr, sums, counts, code, residual, nullptr, nullptr, flags);
+}
+
+int tsdf_dense_sample(tsdf_dense_t* h, const double* points, int64_t n, float* sdf, float* grad, uint8_t* code, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(dense_ray_source(h, &S));
+    return sample(S, points, n, sdf, grad, code, flags);
+}
+
+int tsdf_hash_sample(tsdf_hash_t* h, const double* points, int64_t n, float* sdf, float* grad, uint8_t* code, int flags) {
+    if (!h) return set_error(TSDF_E_ARG, "null handle");
+    RaySource S;
+    TSDF_TRY(hash_ray_source(h, &S));
+    return sample(S, points, n, sdf, grad, code, flags);
 }
 
 int tsdf_track_last_prep_ms(double* ms) {

@@ -167,6 +167,12 @@ SIGNATURES = {
     "tsdf_dense_track_rgbd": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _I],
     "tsdf_hash_track_rgbd": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _P, _P, _P, _P, _I],
     "tsdf_track_last_prep_ms": [_P],
+    "tsdf_dense_track_sdf": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_hash_track_sdf": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_dense_sdf_linearize": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_hash_sdf_linearize": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "tsdf_dense_sample": [_P, _P, _I64, _P, _P, _P, _I],
+    "tsdf_hash_sample": [_P, _P, _I64, _P, _P, _P, _I],
 }
 
 _lib = None

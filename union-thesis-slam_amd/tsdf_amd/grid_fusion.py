@@ -329,7 +329,8 @@ class TSDFVolume:
 
     def track(self, depth_im, cam_intr, pose_guess, *, dist_max=0.1, angle_max_deg=30.0, stride=1, max_iter=10,
               min_inliers=100, eps_rot=1e-5, eps_trans=1e-5, z_near=0.0, z_far=None, z_step=None,
-              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0):
+              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0,
+              method="icp"):
         """The camera pose of a depth frame, tracked against the fused model (tsdf_dense_track,
         DESIGN.md §7e): point-to-plane ICP of depth_im (H,W; uint16 millimetres or metres, as
         integrate() takes it) against this volume's raycast at pose_guess (camera-to-world), both
@@ -346,12 +347,25 @@ class TSDFVolume:
         raycast colour map, weighted by color_weight (metres per intensity level; 0 reproduces the
         geometric track to the byte), residuals above color_max_diff levels rejected.  It observes
         the motions a view of one plane leaves free.  The info then also has color_inliers,
-        color_candidates and color_rms."""
+        color_candidates and color_rms.
+        method="sdf" aligns the frame to the volume's signed distance field itself instead
+        (tsdf_dense_track_sdf): no raycast, no frame normals; angle_max_deg and the z
+        range are not used, color_im raises ValueError (as does any other method name)."""
         from . import tracking
         return tracking.track_call("tsdf_dense_track", self._h, self._vol_bnds, self._voxel_size, depth_im, cam_intr,
                                    pose_guess, dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot,
                                    eps_trans, z_near, z_far, z_step, return_info, invalid_65535, color_im,
-                                   color_weight, color_max_diff)
+                                   color_weight, color_max_diff, method)
+
+    def sample(self, points):
+        """The fused signed distance at world points (N,3) (tsdf_dense_sample): (sdf (N,) f32
+        metres, grad (N,3) f32 -- the gradient of the trilinear interpolant, metres per metre, not
+        normalised, towards positive tsdf --, code (N,) u8: 2 the 8 voxels around the point are not
+        all inside the volume, 3 one of them was never observed, 4 one lies on the truncated
+        plateau (the value is then no distance), 6 a distance).  Value and gradient are 0 for codes
+        2 and 3.  Arrays for an array, CUDA tensors for a contiguous float64 CUDA tensor."""
+        from . import tracking
+        return tracking.sample_call("tsdf_dense_sample", self._h, self.device, points)
 
     def get_point_cloud(self):
         """grid_fusion.py:322-338: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""

@@ -302,13 +302,25 @@ class HashTable:
 
     def track(self, depth_im, cam_intr, pose_guess, *, dist_max=0.1, angle_max_deg=30.0, stride=1, max_iter=10,
               min_inliers=100, eps_rot=1e-5, eps_trans=1e-5, z_near=0.0, z_far=None, z_step=None,
-              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0):
-        """As TSDFVolume.track, against the table's raycast (tsdf_hash_track)."""
+              return_info=False, invalid_65535=False, color_im=None, color_weight=0.001, color_max_diff=40.0,
+              method="icp"):
+        """As TSDFVolume.track, against the table's raycast (tsdf_hash_track), or with method="sdf"
+        against the table's blocks themselves (tsdf_hash_track_sdf)."""
         from . import tracking
         return tracking.track_call("tsdf_hash_track", self._h, self._vol_bounds, self._voxel_size, depth_im, cam_intr,
                                    pose_guess, dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot,
                                    eps_trans, z_near, z_far, z_step, return_info, invalid_65535, color_im,
-                                   color_weight, color_max_diff)
+                                   color_weight, color_max_diff, method)
+
+    def sample(self, points):
+        """The fused signed distance at world points (N,3) (tsdf_hash_sample): (sdf (N,) f32
+        metres, grad (N,3) f32 -- the gradient of the trilinear interpolant, metres per metre, not
+        normalised, towards positive tsdf --, code (N,) u8: 2 the 8 voxels around the point are not
+        all inside the volume, 3 one of them was never observed, 4 one lies on the truncated
+        plateau (the value is then no distance), 6 a distance).  Value and gradient are 0 for codes
+        2 and 3.  Arrays for an array, CUDA tensors for a contiguous float64 CUDA tensor."""
+        from . import tracking
+        return tracking.sample_call("tsdf_hash_sample", self._h, self.device, points)
 
     def extract_mesh(self, normals=True, colors=True, faces=True, keys=False):
         """Marching cubes at level 0 over the table's live blocks (tsdf_hash_extract_mesh): the

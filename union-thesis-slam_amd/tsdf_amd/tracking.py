@@ -8,6 +8,9 @@ from files): frame-to-model point-to-plane ICP on the device.
     for tests and for trackers that keep their own loop.
   * With a colour image (`track(color_im=...)`, `icp_linearize_rgbd`) a photometric term joins the
     geometric one: it observes the motions a single plane leaves free.
+  * `track(method="sdf")`, `sdf_linearize` and `TSDFVolume.sample` / `HashTable.sample` (through
+    `sample_call`): point-to-SDF alignment on the volume itself -- no raycast, no
+    model maps, no frame normals.
 """
 from __future__ import annotations
 
@@ -82,15 +85,20 @@ def _color_image(color_im, name, hw, like_tensor, device):
 
 def track_call(fn, handle, vol_bnds, voxel_size, depth_im, cam_intr, pose_guess, dist_max, angle_max_deg, stride,
                max_iter, min_inliers, eps_rot, eps_trans, z_near, z_far, z_step, return_info, invalid_65535=False,
-               color_im=None, color_weight=COLOR_WEIGHT, color_max_diff=COLOR_MAX_DIFF):
-    """The track entry points' host side (tsdf_dense_track / tsdf_hash_track, and with color_im the
-    _rgbd ones): defaults, the depth frame through encode_depth (or a CUDA tensor read in place),
-    the result as arrays."""
+               color_im=None, color_weight=COLOR_WEIGHT, color_max_diff=COLOR_MAX_DIFF, method="icp"):
+    """The track entry points' host side (tsdf_dense_track / tsdf_hash_track, with color_im the
+    _rgbd ones, with method="sdf" the _sdf ones, which take no z range): defaults, the depth frame
+    through encode_depth (or a CUDA tensor read in place), the result as arrays."""
+    if method not in ("icp", "sdf"):
+        raise ValueError(f"method must be 'icp' or 'sdf', got {method!r}")
+    sdf = method == "sdf"
+    if sdf and color_im is not None:
+        raise ValueError("method='sdf' takes no color_im: the photometric term belongs to the ICP")
     pose = _ffi.f64(pose_guess, 16)
     K = _ffi.f64(cam_intr, 9)
     if z_step is None:
         z_step = float(voxel_size)
-    if z_far is None:
+    if z_far is None and not sdf:
         z_far = default_z_far(vol_bnds, pose, z_near)
     prm = icp_params(dist_max, angle_max_deg, stride, max_iter, min_inliers, eps_rot, eps_trans)
     flags = _ffi.DEPTH_INVALID_65535 if invalid_65535 else 0
@@ -112,7 +120,10 @@ def track_call(fn, handle, vol_bnds, voxel_size, depth_im, cam_intr, pose_guess,
     n_traj = max(int(max_iter), 0) + 1
     traj = np.zeros((n_traj, 4, 4), np.float64) if return_info else None
     cinfo = None
-    if color_im is None:
+    if sdf:
+        _ffi.call(fn + "_sdf", handle, dptr, dk, int(H), int(W), _ffi.ptr(K), _ffi.ptr(pose), ctypes.byref(prm),
+                  _ffi.ptr(out), ctypes.byref(info), _ffi.ptr(traj), flags)
+    elif color_im is None:
         _ffi.call(fn, handle, dptr, dk, int(H), int(W), _ffi.ptr(K), _ffi.ptr(pose), ctypes.byref(prm), float(z_near),
                   float(z_far), float(z_step), _ffi.ptr(out), ctypes.byref(info), _ffi.ptr(traj), flags)
     else:
@@ -265,3 +276,76 @@ def icp_linearize_rgbd(depth, color, frame_intr, rel_pose, model_depth, model_no
             "code": outs[0], "residual": outs[1], "color_sums": sums[28:].copy(), "color_inliers": int(counts[2]),
             "color_candidates": int(counts[3]), "color_A": Ac, "color_b": bc, "color_code": outs[2],
             "color_residual": outs[3]}
+
+
+def sdf_linearize(obj, depth, cam_intr, rel_pose, pose_guess, *, dist_max=0.1, stride=1, codes=True, residuals=True,
+                  invalid_65535=False):
+    """One linearisation of the point-to-SDF alignment (tsdf_dense_sdf_linearize /
+    tsdf_hash_sdf_linearize) of the depth frame (H,W; uint16 mm or metres) seen through
+    cam_intr at rel_pose (frame camera to the guess camera's frame) against the volume of obj (a
+    TSDFVolume or a HashTable) at pose_guess (camera-to-world).  depth is a NumPy array, or a
+    contiguous CUDA tensor on the handle's device (then the code / residual maps come back as CUDA
+    tensors too).  Returns icp_linearize's dict; the codes are 0 not sampled or no depth, 2 cell
+    outside the volume, 3 a corner never observed, 4 a corner on the truncated plateau, 5 further
+    than dist_max or no gradient, 6 inlier."""
+    K, M, G = _ffi.f64(cam_intr, 9), _ffi.f64(rel_pose, 16), _ffi.f64(pose_guess, 16)
+    prm = icp_params(dist_max, stride=stride)
+    flags = _ffi.DEPTH_INVALID_65535 if invalid_65535 else 0
+    if _is_tensor(depth):
+        import torch
+        dk, dtypes = _depth_tensor_kind(depth)
+        H, W = depth.shape
+        dptr = _device_image(depth, "depth", (H, W), dtypes, obj.device)
+        dev = torch.device("cuda", obj.device)
+        code = torch.zeros((H, W), dtype=torch.uint8, device=dev) if codes else None
+        res = torch.zeros((H, W), dtype=torch.float32, device=dev) if residuals else None
+        cptr = None if code is None else code.data_ptr()
+        rptr = None if res is None else res.data_ptr()
+        torch.cuda.synchronize(dev)  # the handle's stream does not follow torch's
+        flags |= _ffi.DEVICE_PTRS
+    else:
+        dk, d = encode_depth(depth)
+        if d.ndim != 2:
+            raise ValueError("depth must be a 2-d image")
+        H, W = d.shape
+        code = np.zeros((H, W), np.uint8) if codes else None
+        res = np.zeros((H, W), np.float32) if residuals else None
+        dptr, cptr, rptr = (_ffi.ptr(x) for x in (d, code, res))
+    sums = np.zeros(28, np.float64)
+    counts = np.zeros(2, np.int64)
+    fn = "tsdf_hash_sdf_linearize" if type(obj).__name__ == "HashTable" else "tsdf_dense_sdf_linearize"
+    _ffi.call(fn, obj._h, dptr, dk, int(H), int(W), _ffi.ptr(K), _ffi.ptr(M), _ffi.ptr(G), ctypes.byref(prm),
+              _ffi.ptr(sums), _ffi.ptr(counts), cptr, rptr, flags)
+    A = np.zeros((6, 6))
+    k = 0
+    for i in range(6):
+        for j in range(i, 6):
+            A[i, j] = A[j, i] = sums[k]
+            k += 1
+    return {"sums": sums, "inliers": int(counts[0]), "candidates": int(counts[1]), "A": A, "b": sums[21:27].copy(),
+            "code": code, "residual": res}
+
+
+def sample_call(fn, handle, device, points):
+    """The sample entry points' host side (tsdf_dense_sample / tsdf_hash_sample): (sdf (N,) f32 metres,
+    grad (N,3) f32, code (N,) u8) at world points (N,3) -- NumPy arrays for an array, CUDA tensors for a
+    contiguous float64 CUDA tensor on the handle's device (anything else raises ValueError)."""
+    if _is_tensor(points):
+        import torch
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be (N, 3)")
+        n = int(points.shape[0])
+        pptr = _device_image(points, "points", (n, 3), (torch.float64,), device)
+        dev = torch.device("cuda", device)
+        out = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros((n, 3), dtype=torch.float32, device=dev),
+               torch.zeros(n, dtype=torch.uint8, device=dev))
+        torch.cuda.synchronize(dev)  # the handle's stream does not follow torch's
+        _ffi.call(fn, handle, pptr, n, *[o.data_ptr() for o in out], _ffi.DEVICE_PTRS)
+        return out
+    P = np.ascontiguousarray(points, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 3:
+        raise ValueError("points must be (N, 3)")
+    n = P.shape[0]
+    out = (np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint8))
+    _ffi.call(fn, handle, _ffi.ptr(P), n, *[_ffi.ptr(o) for o in out], 0)
+    return out
