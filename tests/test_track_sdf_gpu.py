@@ -153,16 +153,17 @@ def test_sdf_linearize_on_a_hash_after_deferred_integrates(hf, gf, tr, lounge_fr
         assert straddle.sum() >= 20 and no_entry.sum() >= 20
 
 
-def follow(obj, tr, frame, K, g, info, tw, device_counts=True, **prm):
+def follow(obj, tr, frame, K, g, info, tw, device_counts=True, index_offset=(0, 0, 0), max_iter=10, **prm):
     """The restatement chain: for each relative pose M_i the device produced, sdf_ref.linearize(M_i)
     and icp_ref.step reproduce M_{i+1} within STEP_TOL, with the same counts (the device's own
-    linearisation at M_i), status, iteration count, rms and norms."""
+    linearisation at M_i), status, iteration count, rms and norms.  tw is the handle's own extent
+    (a slab's starts at index_offset); max_iter is the call's."""
     traj = info["trajectory"]
     assert len(traj) == info["iterations"] + 1 and np.array_equal(traj[0], np.eye(4))
     status = None
     for i in range(info["iterations"]):
         assert status is None
-        lin = S.linearize(frame, K, traj[i], g, *tw, **volume_of(obj), **prm)
+        lin = S.linearize(frame, K, traj[i], g, *tw, index_offset=index_offset, **volume_of(obj), **prm)
         if device_counts:
             got = tr.sdf_linearize(obj, frame, K, traj[i], g, codes=False, residuals=False, **prm)
             assert (got["inliers"], got["candidates"]) == (lin["inliers"], lin["candidates"])
@@ -171,7 +172,7 @@ def follow(obj, tr, frame, K, g, info, tw, device_counts=True, **prm):
         assert err <= STEP_TOL, (i, err)
     if status is None:
         status = I.MAX_ITER
-        assert info["iterations"] == 10
+        assert info["iterations"] == max_iter
     assert info["status"] == status
     assert info["inliers"] == lin["inliers"] and info["candidates"] == lin["candidates"]
     assert abs(info["rms"] - np.sqrt(lin["sums"][27] / lin["inliers"])) <= 1e-12
