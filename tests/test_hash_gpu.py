@@ -310,3 +310,45 @@ def test_hash_at_load_0_9_with_tombstones_matches_dense(hf, monkeypatch, pipe):
     assert st["probe_max"] > 8, st  # chains past one eight-slot group
     for a, b in zip(g.get_state(), h.get_state()):
         assert np.array_equal(a, b)
+
+
+def test_buffer_sets_rotate_across_calls(hf, monkeypatch):
+    """The hash's fused calls rotate the buffer sets from call to call (csrc/tsdf_pipeline.h): with
+    2 frames per launch, calls of 1, 2, 3, 5 and 7 frames on one handle are 1, 1, 2, 3 and 4 batches,
+    so a call starts in set 0, 1, 2, 1 and 1 and the last one wraps the sets and the staging slots.
+    Synchronous and asynchronous, fused and in-line (TSDF_PIPELINE=0): the same state bit for bit,
+    that of a dense grid given the 18 frames in one call; and a dense handle fed the same calls,
+    fused against in-line."""
+    from tsdf_amd import grid_fusion, scene
+    monkeypatch.setenv("TSDF_BATCH", "2")
+    calls = (1, 2, 3, 5, 7)
+    poses = scene.trajectory(sum(calls), seed=0, start=610)
+    d, c = scene.render(poses, scene.make_spheres(0), seed=0, start=610)
+    d, c = np.ascontiguousarray(d.numpy()), np.ascontiguousarray(c.numpy())
+    K = scene.intrinsics()
+    bnds = np.array([[0.0, 10.24]] * 3)
+    Tinv = np.linalg.inv(poses)
+
+    def feed(v, sync=True):
+        f = 0
+        for n in calls:
+            v.integrate_batch(d[f:f + n], c[f:f + n], K, Tinv[f:f + n], sync=sync)
+            f += n
+        v.sync()
+        return v.get_state()
+
+    def same_bits(A, B):
+        return all(a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes() for a, b in zip(A, B))
+
+    g = grid_fusion.TSDFVolume(bnds.copy(), 0.08)
+    g.integrate_batch(d, c, K, Tinv)
+    G = g.get_state()
+    assert (G[1] > 0).any()
+    dense = {}
+    for pipe in ("1", "0"):
+        monkeypatch.setenv("TSDF_PIPELINE", pipe)
+        for sync in (True, False):
+            h = hf.HashTable(bnds.copy(), 0.08, 1 << 16, max_blocks=1 << 12)
+            assert same_bits(feed(h, sync), G), (pipe, sync)
+        dense[pipe] = feed(grid_fusion.TSDFVolume(bnds.copy(), 0.08))
+    assert same_bits(dense["1"], dense["0"]) and same_bits(dense["1"], G)

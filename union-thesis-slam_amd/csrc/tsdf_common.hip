@@ -691,6 +691,28 @@ int Base::launch_prep(const Batch& bt, int dk, int ck, int W, int H, hipStream_t
     return TSDF_OK;
 }
 
+int Base::fill_stage(Stage* sg, const PipeStep& st, int gi, int gc, int cw, int H, int W, unsigned* grid) const {
+    sg->gi = st.i.on ? gi : 0;
+    sg->cw = st.i.on && st.c.on ? cw : 0;
+    sg->gc = st.c.on && sg->cw == 0 ? gc : 0;
+    sg->cg = cull_per_wg();
+    sg->ptx = (W + 63) / 64;
+    sg->pty = (H + 63) / 64;
+    if (st.i.on) {
+        sg->list_i = list_set[st.i.set];
+        sg->count_i = count_set[st.i.set];
+    }
+    if (st.c.on) {
+        sg->list_c = list_set[st.c.set];
+        sg->count_c = count_set[st.c.set];
+    }
+    if (st.p.on) sg->count_p = count_set[st.p.set];
+    const long long g = (long long)sg->gi + sg->gc + (long long)sg->ptx * sg->pty * st.p.n;
+    if (g >= (1ll << 31)) return set_error(TSDF_E_ARG, "fused grid too large");
+    *grid = (unsigned)g;
+    return TSDF_OK;
+}
+
 unsigned Base::grid_for(const void* kernel, int wg) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, wg, 0) != hipSuccess || per_cu < 1)

@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "tsdf_host.h"
+#include "tsdf_integrate.h"
 
 using namespace tsdf;
 
@@ -60,12 +60,10 @@ int dense_run_inline(tsdf_dense* h, int n_frames, const void* depth, int dk, con
     const unsigned grid = h->nz == 4 ? 2 * B.grid_for((const void*)k_integrate<false, 0, 0, true, 4>)
                                      : B.grid_for((const void*)k_integrate<false, 0, 0, true, 8>);
     B.use_set(0);
-    const int nbat = B.batch;
-    for (int f0 = 0; f0 < n_frames; f0 += nbat) {
+    for (int j = 0, nb = pipe_batches(n_frames, B.batch); j < nb; ++j) {
         Batch bt;
-        const int n = n_frames - f0 < nbat ? n_frames - f0 : nbat;
-        const int slot = (f0 / nbat) % kSlots;
-        TSDF_TRY(B.prepare_batch(&bt, depth, dk, color, ck, H, W, K, Tinv, ow, 1.0, flags, f0, n, slot));
+        const PipeStage b = pipe_stage(j, nb, B.batch, n_frames, 0);
+        TSDF_TRY(B.prepare_batch(&bt, depth, dk, color, ck, H, W, K, Tinv, ow, 1.0, flags, b.f0, b.n, b.slot));
         TSDF_TRY(B.launch_prep(bt, dk, ck, W, H, B.stream));
         hipLaunchKernelGGL((k_cull<false>), dim3(cull_grid), dim3(kCullWG), 0, B.stream, B.vol, bt, no_table,
                            B.list, B.count, B.stats);
@@ -73,7 +71,7 @@ int dense_run_inline(tsdf_dense* h, int n_frames, const void* depth, int dk, con
         hipEvent_t e0;
         TSDF_TRY(B.prof.begin(B.stream, &e0));
         bool ow1 = true;
-        for (int i = 0; i < n; ++i) ow1 = ow1 && bt.f[i].ow == 1.0;
+        for (int i = 0; i < b.n; ++i) ow1 = ow1 && bt.f[i].ow == 1.0;
         const ListEntry* L = B.list;
         const int sel = (dk == TSDF_DEPTH_U16_MM ? 0 : 4) | (ck == TSDF_COLOR_RGB8 ? 0 : 2) | (ow1 ? 1 : 0) |
                         (h->nz == 4 ? 8 : 0);
@@ -103,71 +101,24 @@ int dense_run_inline(tsdf_dense* h, int n_frames, const void* depth, int dk, con
         }
         TSDF_HIP(hipGetLastError());
         TSDF_TRY(B.prof.end(B.stream, e0));
-        TSDF_TRY(B.end_batch(flags, slot));
-        B.frames += n;
+        TSDF_TRY(B.end_batch(flags, b.slot));
+        B.frames += b.n;
     }
     return TSDF_OK;
 }
 
-// The fused path (k_fused, tsdf_device.h): launch L runs integrate(L), cull(L+1) and prep(L+2)
-// of the call's batches, L = -2 .. nb-1.  Batch j uses buffer set and staging slot j % kSets.
-// u16 depth + RGB8 with the vectorised prep's alignment only (the bench's and the demos' case).
-int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, const void* color, int H,
-                    int W, const double* K, const double* Tinv, const double* ow, int flags) {
-    Base& B = h->b;
-    TSDF_TRY(B.use_sets(kSets));
-    const int nbat = B.batch;
-    const int nb = (n_frames + nbat - 1) / nbat;
-    const int gi_occ = h->nz == 4 ? (int)B.grid_for((const void*)k_fused<true, 4>, kFusedWG)
-                                  : (int)B.grid_for((const void*)k_fused<true, 8>, kFusedWG);
-    const int gi_full = h->gi_per_cu ? std::min(gi_occ, h->gi_per_cu * B.n_cu) : gi_occ;
-    const int gc_full = (int)B.cull_grid_fused();
-    // texels (Base::texel_for; z-half waves only) for the batches this call prepares
-    const bool tex = h->nz == 4 && B.texel_for(dk, B.n_bricks, Base::kTexelMinBricksDense);
-    struct TexelScope {
-        Base& b;
-        ~TexelScope() { b.texel_now = false; }
-    } tex_scope{B};
-    B.texel_now = tex;
-    Batch bts[kSets];
-    for (int L = -2; L < nb; ++L) {
-        const int jp = L + 2;  // batch prepped by this launch
-        if (jp < nb) {
-            const int f0 = jp * nbat;
-            const int n = n_frames - f0 < nbat ? n_frames - f0 : nbat;
-            B.use_set(jp % kSets);
-            TSDF_TRY(B.prepare_batch(&bts[jp % kSets], depth, dk, color, TSDF_COLOR_RGB8, H, W,
-                                     K, Tinv, ow, 1.0, flags, f0, n, jp % kSlots));
-        }
-        const bool has_i = L >= 0, has_c = L + 1 >= 0 && L + 1 < nb, has_p = jp < nb;
-        static const Batch kNone{};
-        const Batch& bi = has_i ? bts[L % kSets] : kNone;
-        const Batch& bc = has_c ? bts[(L + 1) % kSets] : kNone;
-        const Batch& bp = has_p ? bts[jp % kSets] : kNone;
-        Stage sg{};
-        sg.gi = has_i ? gi_full : 0;
-        // the cull in service waves of the integrate workgroups where the launch has both stages
-        // (Base::cull_waves); the fill launch L = -1 keeps the cull workgroups
-        sg.cw = has_i && has_c ? B.cull_waves() : 0;
-        sg.gc = has_c && sg.cw == 0 ? gc_full : 0;
-        sg.cg = B.cull_per_wg();
-        sg.ptx = (W + 63) / 64;
-        sg.pty = (H + 63) / 64;
-        if (has_i) {
-            sg.list_i = B.list_set[L % kSets];
-            sg.count_i = B.count_set[L % kSets];
-        }
-        if (has_c) {
-            sg.list_c = B.list_set[(L + 1) % kSets];
-            sg.count_c = B.count_set[(L + 1) % kSets];
-        }
-        if (has_p) sg.count_p = B.count_set[jp % kSets];
-        const long long grid = (long long)sg.gi + sg.gc + (has_p ? (long long)sg.ptx * sg.pty * bp.n : 0);
-        if (grid >= (1ll << 31)) return set_error(TSDF_E_ARG, "fused grid too large");
+// The fused path (k_fused, tsdf_device.h) on the shared loop (run_fused, tsdf_integrate.h): the
+// dense grid's part of a launch.
+struct DenseFused {
+    tsdf_dense* h;
+    int dk;
+    bool tex;
+    int gi, gc, cw;
+    int finish(const PipeStep&, Stage&) { return TSDF_OK; }
+    void launch(unsigned grid, const Batch& bi, const Batch& bc, const Batch& bp, const Stage& sg) {
+        Base& B = h->b;
         bool ow1 = true;
         for (int i = 0; i < bi.n; ++i) ow1 = ow1 && bi.f[i].ow == 1.0;
-        hipEvent_t e0 = nullptr;
-        if (has_i) TSDF_TRY(B.prof.begin(B.stream, &e0));
         // (u32 colour registers where the volume is canonical: obs_weight 1 and NZ = 4, tsdf_device.h)
         const bool cu = ow1 && h->nz == 4 && B.vol.canon;
         const int sel = (ow1 ? 1 : 0) | (h->nz == 4 ? 2 : 0) | (dk == TSDF_DEPTH_U16_MM ? 0 : 4) | (cu ? 8 : 0) |
@@ -176,11 +127,11 @@ int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, cons
         switch (sel) {
 #define TSDF_LAUNCH(S, OW_, NZ_, DK_)                                                                   \
     case S:                                                                                             \
-        hipLaunchKernelGGL((k_fused<OW_, NZ_, DK_>), dim3((unsigned)grid), dim3(kFusedWG), 0, B.stream, args); \
+        hipLaunchKernelGGL((k_fused<OW_, NZ_, DK_>), dim3(grid), dim3(kFusedWG), 0, B.stream, args);    \
         break;
 #define TSDF_LAUNCH_CU(S, OW_, NZ_, DK_)                                                                \
     case S:                                                                                             \
-        hipLaunchKernelGGL((k_fused<OW_, NZ_, DK_, true>), dim3((unsigned)grid), dim3(kFusedWG), 0, B.stream, args); \
+        hipLaunchKernelGGL((k_fused<OW_, NZ_, DK_, true>), dim3(grid), dim3(kFusedWG), 0, B.stream, args); \
         break;
             TSDF_LAUNCH(0, false, 8, 0)
             TSDF_LAUNCH(1, true, 8, 0)
@@ -198,14 +149,22 @@ int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, cons
 #undef TSDF_LAUNCH
 #undef TSDF_LAUNCH_CU
         }
-        TSDF_HIP(hipGetLastError());
-        if (has_i) {
-            TSDF_TRY(B.prof.end(B.stream, e0));
-            TSDF_TRY(B.end_batch(flags, L % kSlots));  // batch L's frames: last read by this launch
-            B.frames += bi.n;
-        }
     }
-    return TSDF_OK;
+    int integrated(const Batch&, const Stage&) { return TSDF_OK; }
+    int released() { return TSDF_OK; }
+};
+
+int dense_run_fused(tsdf_dense* h, int n_frames, const void* depth, int dk, const void* color, int H,
+                    int W, const double* K, const double* Tinv, const double* ow, int flags) {
+    Base& B = h->b;
+    TSDF_TRY(B.use_sets(kSets));
+    const int gi_occ = h->nz == 4 ? (int)B.grid_for((const void*)k_fused<true, 4>, kFusedWG)
+                                  : (int)B.grid_for((const void*)k_fused<true, 8>, kFusedWG);
+    // texels (Base::texel_for; z-half waves only) for the batches this call prepares
+    const bool tex = h->nz == 4 && B.texel_for(dk, B.n_bricks, Base::kTexelMinBricksDense);
+    DenseFused pol{h, dk, tex, h->gi_per_cu ? std::min(gi_occ, h->gi_per_cu * B.n_cu) : gi_occ,
+                   (int)B.cull_grid_fused(), B.cull_waves()};
+    return run_fused(B, pol, n_frames, depth, dk, color, H, W, K, Tinv, ow, flags, 0);
 }
 
 int dense_run(tsdf_dense* h, int n_frames, const void* depth, int dk, const void* color, int ck,
@@ -217,14 +176,8 @@ int dense_run(tsdf_dense* h, int n_frames, const void* depth, int dk, const void
     CallGuard guard(B, flags);
     B.note_frames(ck, ow, n_frames, 1.0);
     B.touch_state();
-    // the fused pipeline needs the vectorised prep: u16 or f64 depth + RGB8, W % 4 == 0 and
-    // (device frames) 8-byte u16 / 16-byte f64 depth and 4-byte colour alignment of every frame
-    // (host frames are staged aligned)
-    bool fused = h->fused && ck == TSDF_COLOR_RGB8 && W % 4 == 0 && n_frames > 0;
-    if (fused && (flags & TSDF_DEVICE_PTRS))
-        fused = (uintptr_t)depth % (dk == TSDF_DEPTH_U16_MM ? 8 : 16) == 0 && (uintptr_t)color % 4 == 0 &&
-                ((size_t)H * W) % 4 == 0;
-    if (fused) TSDF_TRY(dense_run_fused(h, n_frames, depth, dk, color, H, W, K, Tinv, ow, flags));
+    if (h->fused && Base::fused_ok(n_frames, depth, dk, color, ck, H, W, flags))
+        TSDF_TRY(dense_run_fused(h, n_frames, depth, dk, color, H, W, K, Tinv, ow, flags));
     else TSDF_TRY(dense_run_inline(h, n_frames, depth, dk, color, ck, H, W, K, Tinv, ow, flags));
     TSDF_TRY(guard.finish());
     if (!(flags & TSDF_ASYNC)) TSDF_HIP(hipStreamSynchronize(B.stream));
@@ -237,13 +190,9 @@ int dense_flush(tsdf_dense* h) {
     if (B.dfr.n == 0) return TSDF_OK;
     const Base::Deferred d = B.dfr;
     B.dfr.n = 0;
-    B.prestaged = d.slot;
-    B.pre_copied = d.copied;
-    const int r = dense_run(h, d.n, B.hst_depth[d.slot], d.dk, B.hst_color[d.slot], d.ck, d.H, d.W, d.K, d.T,
-                            d.ow, TSDF_ASYNC);
-    B.prestaged = -1;
-    B.pre_copied = 0;
-    return r;
+    PrestagedScope pre(B, d);
+    return dense_run(h, d.n, B.hst_depth[d.slot], d.dk, B.hst_color[d.slot], d.ck, d.H, d.W, d.K, d.T, d.ow,
+                     TSDF_ASYNC);
 }
 
 // C-order get/set of the whole shard through a bounded device buffer (<= 64 MiB of rows at a time).
@@ -424,19 +373,9 @@ int tsdf_dense_integrate(tsdf_dense_t* h, const void* depth, int depth_kind, con
     if (!h) return set_error(TSDF_E_ARG, "null handle");
     TSDF_TRY(check_frame_args(depth, depth_kind, color, color_kind, height, width, K, world_to_cam));
     TSDF_HIP(hipSetDevice(h->b.device));
-    Base& B = h->b;
-    if (flags & TSDF_DEFER) {
-        if (flags & TSDF_DEVICE_PTRS) return set_error(TSDF_E_ARG, "TSDF_DEFER takes host frames only");
-        if (B.dfr.n > 0 && !B.defer_same(depth_kind, color_kind, height, width, K)) TSDF_TRY(dense_flush(h));
-        int r = B.defer_push(depth, depth_kind, color, color_kind, height, width, K, world_to_cam, obs_weight);
-        if (r == Base::kDeferFlush) {  // the batch's frames went as u16 and this one cannot
-            TSDF_TRY(dense_flush(h));
-            r = B.defer_push(depth, depth_kind, color, color_kind, height, width, K, world_to_cam, obs_weight);
-        }
-        TSDF_TRY(r);
-        if (B.dfr.n == B.defer_frames) TSDF_TRY(dense_flush(h));
-        return TSDF_OK;
-    }
+    if (flags & TSDF_DEFER)
+        return integrate_deferred(h->b, depth, depth_kind, color, color_kind, height, width, K, world_to_cam,
+                                  obs_weight, flags, [h](bool) { return dense_flush(h); }, [] { return TSDF_OK; });
     TSDF_TRY(dense_flush(h));
     return dense_run(h, 1, depth, depth_kind, color, color_kind, height, width, K, world_to_cam,
                      &obs_weight, flags);

@@ -16,8 +16,6 @@
 #include <cstring>
 #include <thread>
 
-#include "tsdf_host.h"
-
 #ifdef TSDF_HOST_TIMES
 // (diagnostic builds, tools/gpu/dropin_trace.py) host time of the hash drop-in's flush, by part:
 // 0 whole deferred flushes, 1 waiting for a pool report, 2 prepare_batch, 3 kernel launches,
@@ -35,6 +33,8 @@ struct HostTimer {
 #else
 #define TSDF_HOST_TIME(slot) ((void)0)
 #endif
+
+#include "tsdf_integrate.h"  // (after TSDF_HOST_TIME: run_fused carries the markers 2 and 3)
 
 using namespace tsdf;
 
@@ -1010,20 +1010,70 @@ int hash_after_batch(tsdf_hash* h, const Batch& bt, int dk, int ck) {
 constexpr int kCheckLater = 1 << 30;
 int hash_settle(tsdf_hash* h);
 
+// The hash's part of a launch of the shared loop (run_fused, tsdf_integrate.h).
+struct HashFused {
+    tsdf_hash* h;
+    int dk;
+    bool tex, sync, later;
+    int gi, gc, cw;
+    int finish(const PipeStep& st, Stage& sg) {
+        Base& B = h->b;
+        if (st.i.on) sg.res_i = h->d_res + (size_t)st.i.set * B.n_bricks;
+        if (st.c.on) sg.res_c = h->d_res + (size_t)st.c.set * B.n_bricks;
+        // the arrival counter of the commit (a word the prep of that set reset)
+        sg.done = st.c.on ? sg.count_c + kDoneWordC : st.i.on ? sg.count_i + kDoneWord : nullptr;
+        // the previous deferred batch's overflow check (its report; an exact re-run if it skipped
+        // bricks) comes before this batch's integrate -- after this call's own ingest, prep and cull
+        // were issued, so they overlap the previous batch on the GPU
+        if (st.i.on && h->pend.on) TSDF_TRY(hash_settle(h));
+        if (st.i.on || st.c.on) {
+            // every launch with a cull allocates (its cull inserts the next batch's new blocks) and
+            // every integrate may skip bricks: each such launch reports its pool state
+            if (!sync && st.c.on) TSDF_TRY(async_room(h, h->seq));
+            if (sync && !st.i.on) TSDF_TRY(ensure_room(h, true));  // (the call's first cull: last known state)
+            sg.seq = h->seq++;
+        } else {
+            sg.seq = -1;
+        }
+        return TSDF_OK;
+    }
+    void launch(unsigned grid, const Batch& bi, const Batch& bc, const Batch& bp, const Stage& sg) {
+        Base& B = h->b;
+        const FusedHashArgs args{B.vol, bi, bc, bp, B.pool, h->t, B.stats, sg};
+        // (u32 colour registers where the table's blocks are canonical, tsdf_device.h)
+        const bool cu = B.vol.canon;
+        if (tex) {
+            if (cu) hipLaunchKernelGGL((k_fused_hash<2, true>), dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+            else hipLaunchKernelGGL(k_fused_hash<2>, dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+        } else if (dk == TSDF_DEPTH_U16_MM) {
+            if (cu) hipLaunchKernelGGL((k_fused_hash<0, true>), dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+            else hipLaunchKernelGGL(k_fused_hash<0>, dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+        } else {
+            if (cu) hipLaunchKernelGGL((k_fused_hash<1, true>), dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+            else hipLaunchKernelGGL(k_fused_hash<1>, dim3(grid), dim3(kFusedHashWG), 0, B.stream, args);
+        }
+    }
+    // the batch's overflow check: left to the next call (hash_settle), or at once (synchronous
+    // calls: the re-run reads the batch's frames, so before their slot is handed back)
+    int integrated(const Batch& bi, const Stage& sg) {
+        if (later) h->pend = {true, bi, dk, TSDF_COLOR_RGB8, sg.seq};
+        return sync && !later ? hash_after_batch(h, bi, dk, TSDF_COLOR_RGB8) : TSDF_OK;
+    }
+    int released() { return sync && !later ? ensure_room(h, true) : TSDF_OK; }
+};
+
 int hash_run_fused(tsdf_hash* h, int n_frames, const void* depth, int dk, const void* color, int H, int W,
                    const double* K, const double* Tinv, int flags) {
     Base& B = h->b;
     const bool sync = !(flags & TSDF_ASYNC);
-    const int nbat = B.batch;
-    const bool later = sync && (flags & kCheckLater) && n_frames <= nbat;
+    const bool later = sync && (flags & kCheckLater) && n_frames <= B.batch;
     // a pending batch's exact re-run reads its buffer set and staging slot: settle it first if this
     // call reallocates per-batch buffers (first fused call, another image size)
     if (h->pend.on && !(B.n_sets >= kSets && B.pyr_H == H && B.pyr_W == W && B.stage_fits(dk, TSDF_COLOR_RGB8, H, W)))
         TSDF_TRY(hash_settle(h));
     TSDF_TRY(B.use_sets(kSets));
     const int rot = h->set_rot;
-    const auto set_of = [rot](int j) { return (j + rot) % kSets; };
-    const int nb = (n_frames + nbat - 1) / nbat;
+    const int nb = pipe_batches(n_frames, B.batch);
     // a pending deferred batch uses one buffer set, which the loop's prep of batch 2 would reuse
     // (its exact re-run reads it): settle it before a call of several batches (round-4 advisor)
     if (h->pend.on && nb > 1) TSDF_TRY(hash_settle(h));
@@ -1035,104 +1085,15 @@ int hash_run_fused(tsdf_hash* h, int n_frames, const void* depth, int dk, const 
         h->t.ins_list = h->d_ins;
         h->t.ins_cap = B.n_bricks;
     }
-    const int gi_full = (int)B.grid_for((const void*)k_fused_hash<0>, kFusedHashWG);
-    // (a shard that owns no brick -- more shards than bricks -- still runs one cull workgroup, which
-    // lists nothing, like the in-line path's max(1, ...))
-    const int gc_full = h->t.owned ? std::max(1, (h->t.n_owned + 63) / 64) : (int)B.cull_grid_fused();
     // texels (Base::texel_for) by the bricks this handle owns
     const bool tex = B.texel_for(dk, h->t.owned ? (long long)h->t.n_owned : B.n_bricks, Base::kTexelMinBricksHash);
-    struct TexelScope {
-        Base& b;
-        ~TexelScope() { b.texel_now = false; }
-    } tex_scope{B};
-    B.texel_now = tex;
-    Batch bts[kSets];
-    h->set_rot = (rot + nb) % kSets;
-    for (int L = -2; L < nb; ++L) {
-        const int jp = L + 2;
-        if (jp < nb) {
-            const int f0 = jp * nbat;
-            const int n = n_frames - f0 < nbat ? n_frames - f0 : nbat;
-            B.use_set(set_of(jp));
-            // HashTable.integrate ignores obs_weight (hash_fusion.py:141,145): always 1.
-            TSDF_HOST_TIME(2);
-            TSDF_TRY(B.prepare_batch(&bts[jp % kSets], depth, dk, color, TSDF_COLOR_RGB8, H, W,
-                                     K, Tinv, nullptr, 1.0, flags, f0, n, jp % kSlots));
-        }
-        const bool has_i = L >= 0, has_c = L + 1 >= 0 && L + 1 < nb, has_p = jp < nb;
-        static const Batch kNone{};
-        const Batch& bi = has_i ? bts[L % kSets] : kNone;
-        const Batch& bc = has_c ? bts[(L + 1) % kSets] : kNone;
-        const Batch& bp = has_p ? bts[jp % kSets] : kNone;
-        Stage sg{};
-        sg.gi = has_i ? gi_full : 0;
-        sg.gc = has_c ? gc_full : 0;
-        sg.cg = B.cull_per_wg();
-        sg.ptx = (W + 63) / 64;
-        sg.pty = (H + 63) / 64;
-        if (has_i) {
-            sg.list_i = B.list_set[set_of(L)];
-            sg.count_i = B.count_set[set_of(L)];
-            sg.res_i = h->d_res + (size_t)set_of(L) * B.n_bricks;
-        }
-        if (has_c) {
-            sg.list_c = B.list_set[set_of(L + 1)];
-            sg.count_c = B.count_set[set_of(L + 1)];
-            sg.res_c = h->d_res + (size_t)set_of(L + 1) * B.n_bricks;
-        }
-        if (has_p) sg.count_p = B.count_set[set_of(jp)];
-        // the arrival counter of the commit (a word the prep of that set reset)
-        sg.done = has_c ? sg.count_c + kDoneWordC : has_i ? sg.count_i + kDoneWord : nullptr;
-        const long long grid = (long long)sg.gi + sg.gc + (has_p ? (long long)sg.ptx * sg.pty * bp.n : 0);
-        if (grid >= (1ll << 31)) return set_error(TSDF_E_ARG, "fused grid too large");
-        // the previous deferred batch's overflow check (its report; an exact re-run if it skipped
-        // bricks) comes before this batch's integrate -- after this call's own ingest, prep and cull
-        // were issued, so they overlap the previous batch on the GPU
-        if (has_i && h->pend.on) TSDF_TRY(hash_settle(h));
-        if (has_i || has_c) {
-            // every launch with a cull allocates (its cull inserts the next batch's new blocks) and
-            // every integrate may skip bricks: each such launch reports its pool state
-            if (!sync && has_c) TSDF_TRY(async_room(h, h->seq));
-            if (sync && !has_i) TSDF_TRY(ensure_room(h, true));  // (the call's first cull: last known state)
-            sg.seq = h->seq++;
-        } else {
-            sg.seq = -1;
-        }
-        hipEvent_t e0 = nullptr;
-        if (has_i) TSDF_TRY(B.prof.begin(B.stream, &e0));
-        const FusedHashArgs args{B.vol, bi, bc, bp, B.pool, h->t, B.stats, sg};
-        TSDF_HOST_TIME(3);
-        // (u32 colour registers where the table's blocks are canonical, tsdf_device.h)
-        const bool cu = B.vol.canon;
-        if (tex) {
-            if (cu) hipLaunchKernelGGL((k_fused_hash<2, true>), dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-            else hipLaunchKernelGGL(k_fused_hash<2>, dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-        } else if (dk == TSDF_DEPTH_U16_MM) {
-            if (cu) hipLaunchKernelGGL((k_fused_hash<0, true>), dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-            else hipLaunchKernelGGL(k_fused_hash<0>, dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-        } else {
-            if (cu) hipLaunchKernelGGL((k_fused_hash<1, true>), dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-            else hipLaunchKernelGGL(k_fused_hash<1>, dim3((unsigned)grid), dim3(kFusedHashWG), 0, B.stream, args);
-        }
-        TSDF_HIP(hipGetLastError());
-        if (!has_i) continue;
-        TSDF_TRY(B.prof.end(B.stream, e0));
-        B.frames += bi.n;
-        if (later) {
-            TSDF_TRY(B.end_batch(flags, L % kSlots));
-            h->pend.bt = bi;
-            h->pend.dk = dk;
-            h->pend.ck = TSDF_COLOR_RGB8;
-            h->pend.seq = sg.seq;
-            h->pend.on = true;
-        } else if (sync) {
-            TSDF_TRY(hash_after_batch(h, bi, dk, TSDF_COLOR_RGB8));
-            TSDF_TRY(B.end_batch(flags, L % kSlots));
-            TSDF_TRY(ensure_room(h, true));
-        } else {
-            TSDF_TRY(B.end_batch(flags, L % kSlots));
-        }
-    }
+    // (a shard that owns no brick -- more shards than bricks -- still runs one cull workgroup, which
+    // lists nothing, like the in-line path's max(1, ...))
+    HashFused pol{h, dk, tex, sync, later, (int)B.grid_for((const void*)k_fused_hash<0>, kFusedHashWG),
+                  h->t.owned ? std::max(1, (h->t.n_owned + 63) / 64) : (int)B.cull_grid_fused(), 0};
+    h->set_rot = pipe_rot_after(rot, nb);
+    // HashTable.integrate ignores obs_weight (hash_fusion.py:141,145): always 1.
+    TSDF_TRY(run_fused(B, pol, n_frames, depth, dk, color, H, W, K, Tinv, nullptr, flags, rot));
     // the blocks the call's culls inserted that no frame gave an entry (after the last launch, which
     // has no cull: no claim word is pending)
     TSDF_HOST_TIME(4);
@@ -1168,11 +1129,8 @@ int hash_run(tsdf_hash* h, int n_frames, const void* depth, int dk, const void* 
     B.note_frames(ck, nullptr, n_frames, 1.0);
     // (the fused launch is built for power-of-two table sizes: every device table is one)
     const auto p2 = [](long long n) { return n > 0 && (n & (n - 1)) == 0; };
-    bool fused = h->fused && ck == TSDF_COLOR_RGB8 && W % 4 == 0 && n_frames > 0 && p2(h->t.capacity) &&
-                 p2(h->t.shard_cap);
-    if (fused && (flags & TSDF_DEVICE_PTRS))
-        fused = (uintptr_t)depth % (dk == TSDF_DEPTH_U16_MM ? 8 : 16) == 0 && (uintptr_t)color % 4 == 0 &&
-                ((size_t)H * W) % 4 == 0;
+    const bool fused = h->fused && p2(h->t.capacity) && p2(h->t.shard_cap) &&
+                       Base::fused_ok(n_frames, depth, dk, color, ck, H, W, flags);
     if (!fused && h->pend.on) TSDF_TRY(hash_settle(h));  // (the in-line path checks each batch at once)
     if (fused) {
         TSDF_TRY(hash_run_fused(h, n_frames, depth, dk, color, H, W, K, Tinv, flags));
@@ -1181,13 +1139,11 @@ int hash_run(tsdf_hash* h, int n_frames, const void* depth, int dk, const void* 
         return TSDF_OK;
     }
     B.use_set(0);
-    const int nbat = B.batch;
-    for (int f0 = 0; f0 < n_frames; f0 += nbat) {
+    for (int j = 0, nb = pipe_batches(n_frames, B.batch); j < nb; ++j) {
         Batch bt;
-        const int n = n_frames - f0 < nbat ? n_frames - f0 : nbat;
-        const int slot = (f0 / nbat) % kSlots;
+        const PipeStage b = pipe_stage(j, nb, B.batch, n_frames, 0);
         // HashTable.integrate ignores obs_weight (hash_fusion.py:141,145): always 1.
-        TSDF_TRY(B.prepare_batch(&bt, depth, dk, color, ck, H, W, K, Tinv, nullptr, 1.0, flags, f0, n, slot));
+        TSDF_TRY(B.prepare_batch(&bt, depth, dk, color, ck, H, W, K, Tinv, nullptr, 1.0, flags, b.f0, b.n, b.slot));
         TSDF_TRY(B.launch_prep(bt, dk, ck, W, H, B.stream));
         hipLaunchKernelGGL((k_cull<true>), dim3(cull_grid), dim3(kCullWG), 0, B.stream, B.vol, bt, h->t, B.list,
                            B.count, B.stats);
@@ -1201,13 +1157,13 @@ int hash_run(tsdf_hash* h, int n_frames, const void* depth, int dk, const void* 
         hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, B.stream, h->t.st, (long long)h->t.max_blocks,
                            h->t.rb, h->seq++, (const unsigned*)B.count);
         TSDF_HIP(hipGetLastError());
-        B.frames += n;
+        B.frames += b.n;
         if (!sync) {
-            TSDF_TRY(B.end_batch(flags, slot));
+            TSDF_TRY(B.end_batch(flags, b.slot));
             continue;
         }
         TSDF_TRY(hash_after_batch(h, bt, dk, ck));
-        TSDF_TRY(B.end_batch(flags, slot));  // the overflow re-runs above read this batch's frames
+        TSDF_TRY(B.end_batch(flags, b.slot));  // the overflow re-runs above read this batch's frames
         TSDF_TRY(ensure_room(h, true));
     }
     TSDF_TRY(guard.finish());
@@ -1257,13 +1213,11 @@ int hash_flush(tsdf_hash* h, bool wait = true) {
     if (B.dfr.n == 0) return TSDF_OK;
     const Base::Deferred d = B.dfr;
     B.dfr.n = 0;
-    B.prestaged = d.slot;
-    B.pre_copied = d.copied;
-    const int r = hash_run(h, d.n, B.hst_depth[d.slot], d.dk, B.hst_color[d.slot], d.ck, d.H, d.W, d.K, d.T,
-                           wait ? 0 : kCheckLater);
-    B.prestaged = -1;
-    B.pre_copied = 0;
-    TSDF_TRY(r);
+    {
+        PrestagedScope pre(B, d);
+        TSDF_TRY(hash_run(h, d.n, B.hst_depth[d.slot], d.dk, B.hst_color[d.slot], d.ck, d.H, d.W, d.K, d.T,
+                          wait ? 0 : kCheckLater));
+    }
     if (wait) TSDF_TRY(hash_settle(h));
     return TSDF_OK;
 }
@@ -1490,21 +1444,14 @@ int tsdf_hash_integrate(tsdf_hash_t* h, const void* depth, int depth_kind, const
     TSDF_TRY(check_frame_args(depth, depth_kind, color, color_kind, height, width, K, world_to_cam));
     TSDF_HIP(hipSetDevice(h->b.device));
     Base& B = h->b;
-    if (flags & TSDF_DEFER) {
-        if (flags & TSDF_DEVICE_PTRS) return set_error(TSDF_E_ARG, "TSDF_DEFER takes host frames only");
-        if (B.dfr.n > 0 && !B.defer_same(depth_kind, color_kind, height, width, K)) TSDF_TRY(hash_flush(h));
-        // a pending batch's re-run reads its staging slots: settle it before they are reallocated
-        if (h->pend.on && !B.stage_fits(depth_kind, color_kind, height, width)) TSDF_TRY(hash_settle(h));
+    if (flags & TSDF_DEFER)
         // HashTable.integrate ignores obs_weight (hash_fusion.py:141,145): always 1
-        int r = B.defer_push(depth, depth_kind, color, color_kind, height, width, K, world_to_cam, 1.0);
-        if (r == Base::kDeferFlush) {  // the batch's frames went as u16 and this one cannot
-            TSDF_TRY(hash_flush(h));
-            r = B.defer_push(depth, depth_kind, color, color_kind, height, width, K, world_to_cam, 1.0);
-        }
-        TSDF_TRY(r);
-        if (B.dfr.n == B.defer_frames) TSDF_TRY(hash_flush(h, false));
-        return TSDF_OK;
-    }
+        return integrate_deferred(
+            B, depth, depth_kind, color, color_kind, height, width, K, world_to_cam, 1.0, flags,
+            [h](bool wait) { return hash_flush(h, wait); },
+            [&] {  // a pending batch's re-run reads its staging slots: settle it before they are reallocated
+                return h->pend.on && !B.stage_fits(depth_kind, color_kind, height, width) ? hash_settle(h) : TSDF_OK;
+            });
     TSDF_TRY(hash_flush(h));
     return hash_run(h, 1, depth, depth_kind, color, color_kind, height, width, K, world_to_cam, flags);
 }

@@ -11,6 +11,7 @@
 
 #include "tsdf_device.h"
 #include "tsdf_hip.h"
+#include "tsdf_pipeline.h"
 
 #ifndef TSDF_CULL_WAVES_DEFAULT  // service waves per integrate workgroup where the rule applies (Base::cull_waves)
 #define TSDF_CULL_WAVES_DEFAULT 2
@@ -59,12 +60,8 @@ struct Profiler {
     void release();
 };
 
-// Buffer sets: batch j of a call uses set j % kSets (the fused dense pipeline has batches k,
-// k+1 and k+2 in flight in one launch; the in-line path only ever uses set 0).  Host-pointer
-// frames of batch j are staged in slot j % kSlots and stay there until the launch that
-// integrates them ends; the fourth slot lets the DMA of batch k+2 overlap launch k-1.
-constexpr int kSets = 3;
-constexpr int kSlots = 4;
+// kSets buffer sets and kSlots staging slots: which batch of a call owns which, and until when,
+// is the schedule of tsdf_pipeline.h (included above).
 
 // Device buffers of a handle's tracks (tsdf_track.hip), created by the first one.
 struct IcpCtx;
@@ -205,6 +202,19 @@ struct Base {
     int end_batch(int flags, int slot);
     int end_call(int flags);
     int launch_prep(const Batch& bt, int dk, int ck, int W, int H, hipStream_t st);
+    // May a call take the fused path?  It needs the vectorised prep: u16 or f64 depth + RGB8,
+    // W % 4 == 0 and (device frames; host frames are staged aligned) 8-byte u16 / 16-byte f64 depth
+    // and 4-byte colour alignment of every frame.
+    static bool fused_ok(int n, const void* depth, int dk, const void* color, int ck, int H, int W, int flags) {
+        if (ck != TSDF_COLOR_RGB8 || W % 4 != 0 || n <= 0) return false;
+        return !(flags & TSDF_DEVICE_PTRS) || ((uintptr_t)depth % (dk == TSDF_DEPTH_U16_MM ? 8 : 16) == 0 &&
+                                               (uintptr_t)color % 4 == 0 && ((size_t)H * W) % 4 == 0);
+    }
+    // The Stage fields of a fused launch that both handles fill alike, for step `st` of the schedule:
+    // gi / gc workgroups where it integrates / culls -- with both stages and cw > 0 the cull runs in
+    // cw service waves instead -- the prep tiles, the lists and counts.  *grid: the launch's
+    // workgroups (refused from 2^31).
+    int fill_stage(Stage* sg, const PipeStep& st, int gi, int gc, int cw, int H, int W, unsigned* grid) const;
     // Workgroups of the integrate kernel: as many as can be resident (occupancy x CUs), capped
     // by the work there can be (one brick per wave per round).
     unsigned grid_for(const void* kernel, int wg = kWG);
@@ -305,6 +315,26 @@ struct RaySource {
 int dense_ray_source(tsdf_dense_t* h, RaySource* out);
 int hash_ray_source(tsdf_hash_t* h, RaySource* out);
 
+// Texels (Base::texel_now) for the batches one fused call prepares.
+struct TexelScope {
+    Base& b;
+    TexelScope(Base& b_, bool tex) : b(b_) { b.texel_now = tex; }
+    ~TexelScope() { b.texel_now = false; }
+};
+
+// A flush's run finds its (single) batch in the deferred frames' bounce slot (Base::prestaged).
+struct PrestagedScope {
+    Base& b;
+    PrestagedScope(Base& b_, const Base::Deferred& d) : b(b_) {
+        b.prestaged = d.slot;
+        b.pre_copied = d.copied;
+    }
+    ~PrestagedScope() {
+        b.prestaged = -1;
+        b.pre_copied = 0;
+    }
+};
+
 // end_call on every exit path of an integrate call (error returns included).
 struct CallGuard {
     Base& b;
@@ -319,7 +349,6 @@ struct CallGuard {
         if (!done) (void)b.end_call(flags);
     }
 };
-
 
 int check_frame_args(const void* depth, int dk, const void* color, int ck, int H, int W,
                      const double* K, const double* Tinv);
