@@ -392,8 +392,13 @@ int tsdf_hash_integrate_batch(tsdf_hash_t* h, int n_frames, const void* depth, i
  *   insert: creates the entry (block allocated if needed); if tsdf/weight/color are non-NULL
  *           they set the voxel's values, else the voxel keeps (1, 0, 0).  slot[i] = table slot
  *           of the block, local[i] = voxel index inside the block (the reference returns
- *           (bucket, slot)).  Inserting an existing entry finds it (no duplicates).
- *   remove: removed[i] = 1 if the entry existed; a block whose last entry goes is freed. */
+ *           (bucket, slot)).  Inserting an existing entry finds it (no duplicates) and leaves the
+ *           fields that are not given as they are.
+ *   remove: removed[i] = 1 if the entry existed (of a voxel listed twice in one call, one of the
+ *           two); a block whose last entry goes is freed.
+ * A voxel without an entry holds (1, 0, 0): a removed voxel keeps no state, so an insert without
+ * values, or an integrate, after a remove starts from a fresh voxel like the reference's Voxel()
+ * (hash_fusion.py:138-143). */
 int tsdf_hash_lookup(tsdf_hash_t* h, const int64_t* ijk, int64_t n, float* tsdf, float* weight,
                      float* color, uint8_t* found);
 int tsdf_hash_insert(tsdf_hash_t* h, const int64_t* ijk, int64_t n, const float* tsdf,
@@ -409,7 +414,10 @@ int tsdf_hash_info(tsdf_hash_t* h, tsdf_hash_info_t* out);
  *   brick-local order (x*8 + y)*8 + z, occ n x 8 uint64 voxel-entry words (word z, bit x*8+y);
  *   any field pointer may be NULL.  Host pointers, or device pointers with TSDF_DEVICE_PTRS.
  * import: find-or-insert each block (distinct, inside the volume) and overwrite its contents and
- *   entry words (NULL occ: every voxel has an entry).  The table / pool grow as needed. */
+ *   entry words (NULL occ: every voxel has an entry).  A field that is NULL stays as it is in a
+ *   block the table already holds and is the default in a new one.  A voxel whose bit in occ is
+ *   clear has no entry and holds (1, 0, 0) afterwards, whatever the arrays say for it and also in
+ *   a NULL field.  The table / pool grow as needed. */
 int tsdf_hash_export_blocks(tsdf_hash_t* h, int32_t* bxyz, float* tsdf, float* weight, float* color,
                             uint64_t* occ, int64_t* n_blocks, int flags);
 int tsdf_hash_import_blocks(tsdf_hash_t* h, const int32_t* bxyz, int64_t n_blocks, const float* tsdf,

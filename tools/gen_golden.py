@@ -16,6 +16,8 @@ Fixtures written (data only -- inputs and expected outputs, no reference source)
   golden/dense_c1.npz          lounge f0-f2 -> 128^3 @ 4 cm, reference grid CPU path, per frame (G2)
   golden/dense_c1_ow.npz       same with obs_weight = 1.0, 0.7, 2.5 (mixed f32/f64 colour path)
   golden/hash_c1.npz           lounge f0-f2 -> 128^3 @ 4 cm, reference HashTable.integrate (G2h)
+  golden/hash_c1_remove.npz    lounge f0, remove_hash_entry over a rule's set, lounge f1: the returns,
+                               entry counts, the removed voxels that are back, a state digest (G2r)
   golden/synth_c1.npz          two synthetic frames (tsdf_amd.scene) -> 128^3 @ 8 cm room (G2s)
   golden/lounge2cm_kat.json    lounge 2 cm, frames 0-9: per-frame counts + final-state digest (G3)
   golden/lounge512_kat.json    lounge f0 -> 512^3 @ 2 cm: count + digest (G5)
@@ -199,6 +201,51 @@ def inner():
             res["f%d_collisions" % f] = np.int64(ht.get_num_collisions())
             print("hash_c1 frame", f, "entries", len(pos), "buckets", ht.get_num_non_empty_buckets())
         np.savez_compressed(os.path.join(GOLD, "hash_c1.npz"), **res)
+
+    # ---- G2r hash config 1 with a removal between two frames ---------------------------------
+    # lounge f0, remove_hash_entry over a set taken from hash_c1.npz's f0_pos (tests/hash_model.py
+    # removal_rule: every third entry, plus every entry of every fifth block), lounge f1
+    if want("hash_c1_remove"):
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        sys.path.insert(0, os.path.join(REPO, "oracle"))
+        from hash_model import removal_rule
+        from data_structures import hash_entry as he
+        f0_pos = np.load(os.path.join(GOLD, "hash_c1.npz"))["f0_pos"]
+        idx = removal_rule(f0_pos)
+        ht = hash_fusion.HashTable(np.array(C1_BNDS), 0.04, 1000000, 0.75, False)
+        _, depth, rgb, pose = load_lounge(0)
+        ht.integrate(rgb, depth, cam_intr, pose, obs_weight=1.0)
+        ret = np.array([ht.remove_hash_entry(he.HashEntry([int(v) for v in p], None, None)) for p in f0_pos[idx]],
+                       np.uint8)
+        res = {"remove_idx": idx.astype(np.int32), "remove_ret": ret,
+               "entries_after_remove": np.int64(ht.count_num_hash_entries()),
+               "nonempty_after_remove": np.int64(ht.get_num_non_empty_buckets())}
+        _, depth, rgb, pose = load_lounge(1)
+        ht.integrate(rgb, depth, cam_intr, pose, obs_weight=1.0)
+        pos, sdf, w, col = [], [], [], []
+        for b in ht._hash_table:
+            if b is None:
+                continue
+            for j in range(5):
+                e = b.get_ith_entry(j)
+                if e is not None and e.get_voxel() is not None:
+                    pos.append([int(p) for p in e.get_position()])
+                    sdf.append(float(e.get_voxel().get_sdf()))
+                    w.append(float(e.get_voxel()._weight))
+                    col.append(float(e.get_voxel().get_color()))
+        pos = np.array(pos, np.int64)
+        order = np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))
+        pos, sdf, w, col = pos[order], np.array(sdf)[order], np.array(w)[order], np.array(col)[order]
+        lin = np.ravel_multi_index(tuple(pos.T), (128, 128, 128))
+        back = np.isin(lin, np.ravel_multi_index(tuple(f0_pos[idx].T), (128, 128, 128)))
+        res.update(entries_f1=np.int64(ht.count_num_hash_entries()), back_pos=pos[back].astype(np.int16),
+                   back_sdf=sdf[back], back_weight=w[back].astype(np.float32), back_color=col[back].astype(np.float32),
+                   state_sha256=np.array(digest(pos, sdf, w, col)))
+        assert np.array_equal(res["back_weight"].astype(np.float64), w[back])
+        assert np.array_equal(res["back_color"].astype(np.float64), col[back])
+        print("hash_c1_remove removed", int(ret.sum()), "of", len(ret), "entries", int(res["entries_after_remove"]),
+              "->", int(res["entries_f1"]), "back", int(back.sum()), "weights", np.unique(w[back]))
+        np.savez_compressed(os.path.join(GOLD, "hash_c1_remove.npz"), **res)
 
     # ---- G2s synthetic frames into 128^3 @ 8 cm of the room ----------------------------
     if want("synth"):

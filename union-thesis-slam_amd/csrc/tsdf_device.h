@@ -174,7 +174,12 @@ struct PoolReport {
 struct Table {
     unsigned long long* keys;   // capacity slots; kEmpty / kTomb / packed brick key
     int* vals;                  // pool block of each slot
-    unsigned long long* occ;    // [max_blocks][8] voxel-entry bits (word = z, bit = x*8+y)
+    // [max_blocks][8] voxel-entry bits (word = z, bit = x*8+y).  Invariant: in a block handed out, a
+    // voxel whose bit is clear holds (1, 0, 0) in the pool.  The readers look at the bit; the writers
+    // (integrate_brick's loads of an existing block, k_set_voxels with a field not given) do not and
+    // rely on it, so whoever clears a bit restores the values: k_remove_voxels, k_write_blocks and
+    // the initialisation of a block as it is handed out.
+    unsigned long long* occ;
     int* free_list;
     ListEntry* overflow;        // list entries skipped this launch
     PoolState* st;

@@ -340,6 +340,12 @@ __global__ void k_insert_blocks(Table t, Pool pool, const unsigned long long* ke
     long long s = ref_hash(bx, by, bz, t.capacity, t.int_bits);
     long long tomb = -1;
     int b = -1;
+    // The key is absent once the probe has met an empty slot (nothing removes during the kernel and
+    // no other thread holds this key).  From then on the first free slot is claimed where it is met.
+    // A thread that lost a tombstone used to walk to the next empty slot again before it tried the
+    // next one: 150 keys inserted into one run of 150 tombstones among 300 slots spent the loop's
+    // 2 * capacity steps on those walks and failed with "table or pool full".
+    bool absent = false;
     blk_out[i] = -1;
     slot_out[i] = -1;
     for (long long m = 0; m < 2 * t.capacity; ++m) {
@@ -350,7 +356,8 @@ __global__ void k_insert_blocks(Table t, Pool pool, const unsigned long long* ke
             return;  // (a spare block from a lost race stays unused)
         }
         if (k == kTomb && tomb < 0) tomb = s;
-        if (k == kEmpty) {
+        if (k == kEmpty) absent = true;
+        if (k == kEmpty || (absent && tomb >= 0)) {
             const long long target = tomb >= 0 ? tomb : s;
             const unsigned long long expect = tomb >= 0 ? kTomb : kEmpty;
             if (b < 0) b = pool_alloc(t);
@@ -391,7 +398,10 @@ __global__ void k_set_voxels(Vol v, Table t, Pool pool, const long long* ijk, lo
     if (ic) pool.color[j] = ic[i];
 }
 
-__global__ void k_remove_voxels(Vol v, Table t, const long long* ijk, long long n,
+// The voxel whose entry bit this thread cleared goes back to (1, 0, 0) (the invariant of Table::occ:
+// integrate_brick and k_set_voxels read the pool without looking at the bit).  Of duplicates in one
+// call exactly one thread sees the bit set: one writer.
+__global__ void k_remove_voxels(Vol v, Table t, Pool pool, const long long* ijk, long long n,
                                 unsigned char* removed) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -404,6 +414,12 @@ __global__ void k_remove_voxels(Vol v, Table t, const long long* ijk, long long 
             const unsigned long long bit = 1ull << (local >> 3);
             const unsigned long long old = atomicAnd(&t.occ[blk * 8 + (local & 7)], ~bit);
             r = (old & bit) ? 1 : 0;
+            if (r) {
+                const size_t j = (size_t)blk * kBrickVox + local;
+                pool.tsdf[j] = 1.0f;
+                pool.weight[j] = 0.0f;
+                pool.color[j] = 0.0f;
+            }
         }
     }
     if (removed) removed[i] = r;
@@ -580,8 +596,22 @@ __global__ void k_export_blocks(Table t, Pool pool, unsigned long long* counter,
     }
 }
 
+// One field of an imported block's half column (4 voxels of lane x*8+y): the caller's values, or
+// the block's own where the field is not given, and the field's default wherever `absent` says the
+// voxel has no entry (bit k: voxel k of the four).
+__device__ inline void write_field(float* dst, const float* src, unsigned absent, float dflt) {
+    if (!src && !absent) return;
+    float4 q = *(const float4*)(src ? src : dst);
+    if (absent & 1u) q.x = dflt;
+    if (absent & 2u) q.y = dflt;
+    if (absent & 4u) q.z = dflt;
+    if (absent & 8u) q.w = dflt;
+    *(float4*)dst = q;
+}
+
 // Imported blocks in (one wave per block; blk from k_insert_blocks): contents and entry words
-// overwrite the block.
+// overwrite the block.  A voxel whose bit in the stored words is clear gets (1, 0, 0) whatever the
+// caller passed for it, also in a field that is not given (the invariant of Table::occ).
 __global__ void k_write_blocks(Table t, Pool pool, const int* blk, long long n, const float* it, const float* iw,
                                const float* ic, const unsigned long long* iocc) {
     const int lane = threadIdx.x & 63;
@@ -594,9 +624,14 @@ __global__ void k_write_blocks(Table t, Pool pool, const int* blk, long long n, 
         const size_t dst = (size_t)b * kBrickVox + (size_t)lane * 8, src = (size_t)i * kBrickVox + (size_t)lane * 8;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (it) *(float4*)(pool.tsdf + dst + 4 * h) = *(const float4*)(it + src + 4 * h);
-            if (iw) *(float4*)(pool.weight + dst + 4 * h) = *(const float4*)(iw + src + 4 * h);
-            if (ic) *(float4*)(pool.color + dst + 4 * h) = *(const float4*)(ic + src + 4 * h);
+            unsigned absent = 0;  // voxel z = 4h + k of this lane: word z, bit lane
+            if (iocc) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) absent |= (unsigned)(~(iocc[8 * i + 4 * h + k] >> lane) & 1ull) << k;
+            }
+            write_field(pool.tsdf + dst + 4 * h, it ? it + src + 4 * h : nullptr, absent, 1.0f);
+            write_field(pool.weight + dst + 4 * h, iw ? iw + src + 4 * h : nullptr, absent, 0.0f);
+            write_field(pool.color + dst + 4 * h, ic ? ic + src + 4 * h : nullptr, absent, 0.0f);
         }
     }
 }
@@ -1566,7 +1601,7 @@ int tsdf_hash_remove(tsdf_hash_t* h, const int64_t* ijk, int64_t n, uint8_t* rem
         bufs.add(drem);
     }
     hipLaunchKernelGGL(k_remove_voxels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, B.stream, B.vol,
-                       h->t, (const long long*)dijk, (long long)n, (unsigned char*)drem);
+                       h->t, B.pool, (const long long*)dijk, (long long)n, (unsigned char*)drem);
     TSDF_HIP(hipGetLastError());
     if (!keys.empty()) {
         TSDF_TRY(upload(h, keys.data(), sizeof(unsigned long long) * keys.size(), &dkeys));
