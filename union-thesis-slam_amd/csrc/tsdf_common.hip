@@ -724,20 +724,19 @@ unsigned Base::grid_for(const void* kernel, int wg) {
 }
 
 int Base::check_canon(long long n_vox) {
+    int bad = 0;  // (read back: declared before the owner of what it is read from)
+    DevBufs bufs;
     int* d = nullptr;
-    int bad = 0;
-    TSDF_HIP(hipMalloc(&d, sizeof(int)));
-    hipError_t e = hipMemsetAsync(d, 0, sizeof(int), stream);
-    if (e == hipSuccess && n_vox > 0) {
+    TSDF_TRY(bufs.alloc(&d, 1));
+    TSDF_HIP(hipMemsetAsync(d, 0, sizeof(int), stream));
+    if (n_vox > 0) {
         const long long want = (n_vox + 255) / 256;
         hipLaunchKernelGGL(k_check_canon, dim3((unsigned)std::min<long long>(want, (long long)n_cu * 16)), dim3(256),
                            0, stream, pool.weight, pool.color, (size_t)n_vox, d);
-        e = hipGetLastError();
+        TSDF_HIP(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d, sizeof(int), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d);
-    TSDF_HIP(e);
+    TSDF_HIP(hipMemcpyAsync(&bad, d, sizeof(int), hipMemcpyDeviceToHost, stream));
+    TSDF_HIP(hipStreamSynchronize(stream));
     vol.canon = bad ? 0 : 1;
     return TSDF_OK;
 }
@@ -869,17 +868,15 @@ int tsdf_hash_keys(const int64_t* xyz, int64_t n, int64_t table_size, int int_bi
         return set_error(TSDF_E_ARG, "tsdf_hash_keys: bad arguments");
     if (n == 0) return TSDF_OK;
     TSDF_HIP(hipSetDevice(device));
+    DevBufs bufs;
     long long *dx = nullptr, *dout = nullptr;
-    TSDF_HIP(hipMalloc(&dx, sizeof(long long) * 3 * n));
-    TSDF_HIP(hipMalloc(&dout, sizeof(long long) * n));
+    TSDF_TRY(bufs.alloc(&dx, 3 * (size_t)n));
+    TSDF_TRY(bufs.alloc(&dout, (size_t)n));
     TSDF_HIP(hipMemcpy(dx, xyz, sizeof(long long) * 3 * n, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_hash_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr,
                        (const long long*)dx, (long long)n, (long long)table_size, int_bits, dout);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(long long) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(dx);
-    (void)hipFree(dout);
-    TSDF_HIP(e);
+    TSDF_HIP(hipGetLastError());
+    TSDF_HIP(hipMemcpy(out, dout, sizeof(long long) * n, hipMemcpyDeviceToHost));
     return TSDF_OK;
 }
 

@@ -204,45 +204,33 @@ int dense_xfer(tsdf_dense* h, float* tsdf_, float* weight_, float* color_, bool 
     const size_t yz = (size_t)B.vol.dims[1] * B.vol.dims[2];
     const long long X = B.vol.dims[0];
     const long long chunk = std::max<long long>(1, std::min<long long>(X, (64ll << 20) / (long long)(yz * sizeof(float))));
+    DevBufs bufs;
     float* tmp = nullptr;
-    TSDF_HIP(hipMalloc(&tmp, (size_t)chunk * yz * sizeof(float)));
+    TSDF_TRY(bufs.alloc(&tmp, (size_t)chunk * yz));
     float* host[3] = {tsdf_, weight_, color_};
     float* dev[3] = {B.pool.tsdf, B.pool.weight, B.pool.color};
-    hipError_t e = hipSuccess;
     const unsigned grid = (unsigned)std::min<size_t>(((size_t)chunk * yz + 255) / 256, (size_t)B.n_cu * 16);
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) {
+    for (int k = 0; k < 3; ++k) {
         if (!host[k]) continue;
-        for (long long r0 = 0; r0 < X && e == hipSuccess; r0 += chunk) {
+        for (long long r0 = 0; r0 < X; r0 += chunk) {
             const long long nr = std::min(chunk, X - r0);
             const size_t bytes = (size_t)nr * yz * sizeof(float);
             if (get) {
                 hipLaunchKernelGGL(k_rows<true>, dim3(grid), dim3(256), 0, B.stream, B.vol, (const long long*)nullptr, r0,
                                    nr, dev[k], tmp);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(host[k] + (size_t)r0 * yz, tmp, bytes, hipMemcpyDeviceToHost, B.stream);
+                TSDF_HIP(hipGetLastError());
+                TSDF_HIP(hipMemcpyAsync(host[k] + (size_t)r0 * yz, tmp, bytes, hipMemcpyDeviceToHost, B.stream));
             } else {
-                e = hipMemcpyAsync(tmp, host[k] + (size_t)r0 * yz, bytes, hipMemcpyHostToDevice, B.stream);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(k_rows<false>, dim3(grid), dim3(256), 0, B.stream, B.vol, (const long long*)nullptr,
-                                       r0, nr, dev[k], tmp);
-                    e = hipGetLastError();
-                }
+                TSDF_HIP(hipMemcpyAsync(tmp, host[k] + (size_t)r0 * yz, bytes, hipMemcpyHostToDevice, B.stream));
+                hipLaunchKernelGGL(k_rows<false>, dim3(grid), dim3(256), 0, B.stream, B.vol, (const long long*)nullptr,
+                                   r0, nr, dev[k], tmp);
+                TSDF_HIP(hipGetLastError());
             }
-            if (e == hipSuccess) e = hipStreamSynchronize(B.stream);  // tmp is reused by the next chunk
+            TSDF_HIP(hipStreamSynchronize(B.stream));  // tmp is reused by the next chunk
         }
     }
-    (void)hipFree(tmp);
-    TSDF_HIP(e);
     return TSDF_OK;
 }
-
-struct DevPtrs {
-    std::vector<void*> p;
-    ~DevPtrs() {
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-    }
-};
 
 }  // namespace
 
@@ -454,25 +442,21 @@ int tsdf_dense_extract_mesh_halo(tsdf_dense_t* h, int64_t global_x, const int64_
     TSDF_TRY(dense_flush(h));
     MeshDomain d;
     TSDF_TRY(mesh_domain(B.vol, global_x, halo_gx, n_halo, &d));
-    const size_t hb = (size_t)n_halo * B.vol.dims[1] * B.vol.dims[2] * sizeof(float);
+    const size_t hn = (size_t)n_halo * B.vol.dims[1] * B.vol.dims[2], hb = hn * sizeof(float);
     const float *ht = halo_tsdf, *hc = halo_color;
-    float *ut = nullptr, *uc = nullptr;
-    int r = TSDF_OK;
+    DevBufs bufs;
     if (n_halo > 0 && !(flags & TSDF_DEVICE_PTRS)) {  // host halo rows: upload them for the call
-        hipError_t e = hipMalloc(&ut, hb);
-        if (e == hipSuccess) e = hipMalloc(&uc, hb);
-        if (e == hipSuccess) e = hipMemcpyAsync(ut, halo_tsdf, hb, hipMemcpyHostToDevice, B.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(uc, halo_color, hb, hipMemcpyHostToDevice, B.stream);
-        if (e != hipSuccess) r = set_error(TSDF_E_HIP, "halo upload: %s", hipGetErrorString(e));
+        float *ut = nullptr, *uc = nullptr;
+        TSDF_TRY(bufs.alloc(&ut, hn));
+        TSDF_TRY(bufs.alloc(&uc, hn));
+        TSDF_HIP(hipMemcpyAsync(ut, halo_tsdf, hb, hipMemcpyHostToDevice, B.stream));
+        TSDF_HIP(hipMemcpyAsync(uc, halo_color, hb, hipMemcpyHostToDevice, B.stream));
         ht = ut;
         hc = uc;
     } else if (n_halo > 0) {
         TSDF_HIP(hipDeviceSynchronize());  // the caller's producer (e.g. a collective) may be on another stream
     }
-    if (r == TSDF_OK) r = extract_mesh(B, B.pool, h->mesh, d, ht, hc);
-    if (ut) (void)hipFree(ut);
-    if (uc) (void)hipFree(uc);
-    TSDF_TRY(r);
+    TSDF_TRY(extract_mesh(B, B.pool, h->mesh, d, ht, hc));
     *n_verts = h->mesh.n_verts;
     *n_tris = h->mesh.n_tris;
     return TSDF_OK;
@@ -502,10 +486,9 @@ int tsdf_dense_get_rows(tsdf_dense_t* h, const int64_t* rows, int64_t n_rows, fl
             return set_error(TSDF_E_ARG, "local row %lld outside [0, %d)", (long long)rows[i], B.vol.dims[0]);
     const size_t yz = (size_t)B.vol.dims[1] * B.vol.dims[2];
     const size_t bytes = (size_t)n_rows * yz * sizeof(float);
-    DevPtrs bufs;
+    DevBufs bufs;
     long long* drows = nullptr;
-    TSDF_HIP(hipMalloc(&drows, sizeof(long long) * n_rows));
-    bufs.p.push_back(drows);
+    TSDF_TRY(bufs.alloc(&drows, (size_t)n_rows));
     TSDF_HIP(hipMemcpyAsync(drows, rows, sizeof(long long) * n_rows, hipMemcpyHostToDevice, B.stream));
     float* out[3] = {tsdf_, weight_, color_};
     float* dev[3] = {B.pool.tsdf, B.pool.weight, B.pool.color};
@@ -514,8 +497,7 @@ int tsdf_dense_get_rows(tsdf_dense_t* h, const int64_t* rows, int64_t n_rows, fl
         if (!out[k]) continue;
         float* dst = out[k];
         if (!(flags & TSDF_DEVICE_PTRS)) {
-            TSDF_HIP(hipMalloc(&dst, bytes));
-            bufs.p.push_back(dst);
+            TSDF_TRY(bufs.alloc(&dst, (size_t)n_rows * yz));
         }
         hipLaunchKernelGGL(k_rows<true>, dim3(grid), dim3(256), 0, B.stream, B.vol, (const long long*)drows, 0ll,
                            (long long)n_rows, dev[k], dst);

@@ -103,6 +103,15 @@ __global__ void k_init_keys(unsigned long long* k, int n, unsigned long long v) 
     if (i < n) k[i] = v;
 }
 
+// The call's own stream, destroyed on every exit path (after the call's buffers are freed: it is
+// declared before their owner).
+struct CallStream {
+    hipStream_t s = nullptr;
+    ~CallStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -125,57 +134,50 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     const bool dptr = flags & TSDF_DEVICE_PTRS;
     const int inval = (flags & TSDF_DEPTH_INVALID_65535) ? 1 : 0;
     const int chunk = dptr ? n_frames : std::min(n_frames, 64);
-    hipStream_t s = nullptr;
-    unsigned long long *maxk = nullptr, *bk = nullptr;
-    double *dK = nullptr, *dpose = nullptr, *dpts = nullptr;
-    void* stage = nullptr;
     int cu = 256;
     (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&maxk, sizeof(unsigned long long) * n_frames);
-    if (e == hipSuccess) e = hipMalloc(&bk, sizeof(unsigned long long) * 6);
-    if (e == hipSuccess) e = hipMalloc(&dK, sizeof(double) * 9);
-    if (e == hipSuccess) e = hipMalloc(&dpose, sizeof(double) * 16 * n_frames);
-    if (e == hipSuccess && frustum_pts) e = hipMalloc(&dpts, sizeof(double) * 15 * n_frames);
-    if (e == hipSuccess && !dptr) e = hipMalloc(&stage, esz * npx * chunk);
-    if (e == hipSuccess) e = hipMemcpyAsync(dK, K, sizeof(double) * 9, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dpose, cam_poses, sizeof(double) * 16 * n_frames, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_init_keys, dim3((n_frames + 255) / 256), dim3(256), 0, s, maxk, n_frames, 0ull);
-        hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk, 3, ~0ull);
-        hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk + 3, 3, 0ull);
-        e = hipGetLastError();
-    }
+    std::vector<unsigned long long> hk(n_frames), hb(6);  // (read back: declared before the owners)
+    CallStream cs;
+    TSDF_HIP(hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking));
+    hipStream_t s = cs.s;
+    DevBufs bufs;
+    unsigned long long *maxk = nullptr, *bk = nullptr;
+    double *dK = nullptr, *dpose = nullptr, *dpts = nullptr;
+    char* stage = nullptr;
+    TSDF_TRY(bufs.alloc(&maxk, (size_t)n_frames));
+    TSDF_TRY(bufs.alloc(&bk, 6));
+    TSDF_TRY(bufs.alloc(&dK, 9));
+    TSDF_TRY(bufs.alloc(&dpose, 16 * (size_t)n_frames));
+    if (frustum_pts) TSDF_TRY(bufs.alloc(&dpts, 15 * (size_t)n_frames));
+    if (!dptr) TSDF_TRY(bufs.alloc(&stage, esz * npx * chunk));
+    TSDF_HIP(hipMemcpyAsync(dK, K, sizeof(double) * 9, hipMemcpyHostToDevice, s));
+    TSDF_HIP(hipMemcpyAsync(dpose, cam_poses, sizeof(double) * 16 * n_frames, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_init_keys, dim3((n_frames + 255) / 256), dim3(256), 0, s, maxk, n_frames, 0ull);
+    hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk, 3, ~0ull);
+    hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk + 3, 3, 0ull);
+    TSDF_HIP(hipGetLastError());
     // enough workgroups per frame to stream the image at full HBM rate
     const unsigned per_frame = (unsigned)std::max(1ll, std::min<long long>((npx + 4095) / 4096, std::max(1, 4 * cu / std::max(1, chunk))));
-    for (int f0 = 0; f0 < n_frames && e == hipSuccess; f0 += chunk) {
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
         const int m = std::min(chunk, n_frames - f0);
         const char* src = (const char*)depth + esz * npx * f0;
         if (!dptr) {
-            e = hipMemcpyAsync(stage, src, esz * npx * m, hipMemcpyHostToDevice, s);
-            src = (const char*)stage;
+            TSDF_HIP(hipMemcpyAsync(stage, src, esz * npx * m, hipMemcpyHostToDevice, s));
+            src = stage;
         }
-        if (e != hipSuccess) break;
         if (depth_kind == TSDF_DEPTH_U16_MM)
             hipLaunchKernelGGL(k_frame_max<0>, dim3(per_frame, m), dim3(kMaxWG), 0, s, (const void*)src, npx, inval, maxk + f0);
         else
             hipLaunchKernelGGL(k_frame_max<1>, dim3(per_frame, m), dim3(kMaxWG), 0, s, (const void*)src, npx, inval, maxk + f0);
-        e = hipGetLastError();
+        TSDF_HIP(hipGetLastError());
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_frustum, dim3((n_frames + 63) / 64), dim3(64), 0, s, n_frames, height, width,
-                           (const double*)dK, (const double*)dpose, (const unsigned long long*)maxk, dpts, bk);
-        e = hipGetLastError();
-    }
-    std::vector<unsigned long long> hk(n_frames), hb(6);
-    if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bk, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && max_depth) e = hipMemcpyAsync(hk.data(), maxk, sizeof(unsigned long long) * n_frames, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && frustum_pts) e = hipMemcpyAsync(frustum_pts, dpts, sizeof(double) * 15 * n_frames, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (void* p : {(void*)maxk, (void*)bk, (void*)dK, (void*)dpose, (void*)dpts, stage})
-        if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-    TSDF_HIP(e);
+    hipLaunchKernelGGL(k_frustum, dim3((n_frames + 63) / 64), dim3(64), 0, s, n_frames, height, width, (const double*)dK,
+                       (const double*)dpose, (const unsigned long long*)maxk, dpts, bk);
+    TSDF_HIP(hipGetLastError());
+    TSDF_HIP(hipMemcpyAsync(hb.data(), bk, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, s));
+    if (max_depth) TSDF_HIP(hipMemcpyAsync(hk.data(), maxk, sizeof(unsigned long long) * n_frames, hipMemcpyDeviceToHost, s));
+    if (frustum_pts) TSDF_HIP(hipMemcpyAsync(frustum_pts, dpts, sizeof(double) * 15 * n_frames, hipMemcpyDeviceToHost, s));
+    TSDF_HIP(hipStreamSynchronize(s));
     if (max_depth)
         for (int f = 0; f < n_frames; ++f) max_depth[f] = dval(hk[f]);
     // the demo's np.minimum / np.maximum with the incoming bounds (it starts from zeros)

@@ -645,29 +645,6 @@ __global__ void k_fill_dense(float* t, float* w, float* c, size_t n) {
     }
 }
 
-// Device buffers freed on every exit path unless keep() is called (the error paths of a
-// multi-buffer allocation free what was already allocated).
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() {
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-    }
-    void* add(void* q) {
-        p.push_back(q);
-        return q;
-    }
-    void keep() { p.clear(); }
-};
-
-template <typename T>
-int dev_alloc(DevBufs& bufs, T** out, size_t bytes) {
-    *out = nullptr;
-    TSDF_HIP(hipMalloc((void**)out, bytes));
-    bufs.add(*out);
-    return TSDF_OK;
-}
-
 int read_state(tsdf_hash* h) {
     TSDF_HIP(hipMemcpyAsync(&h->host_st, h->t.st, sizeof(PoolState), hipMemcpyDeviceToHost, h->b.stream));
     TSDF_HIP(hipStreamSynchronize(h->b.stream));
@@ -704,11 +681,11 @@ int grow_pool(tsdf_hash* h, long long new_max) {
     int* nf;
     TSDF_HIP(hipStreamSynchronize(B.stream));
     DevBufs fresh;  // freed again if any allocation or copy fails
-    TSDF_TRY(dev_alloc(fresh, &nt, nn * kBrickVox * sizeof(float)));
-    TSDF_TRY(dev_alloc(fresh, &nw, nn * kBrickVox * sizeof(float)));
-    TSDF_TRY(dev_alloc(fresh, &nc, nn * kBrickVox * sizeof(float)));
-    TSDF_TRY(dev_alloc(fresh, &no, nn * 8 * sizeof(unsigned long long)));
-    TSDF_TRY(dev_alloc(fresh, &nf, nn * sizeof(int)));
+    TSDF_TRY(fresh.alloc(&nt, nn * kBrickVox));
+    TSDF_TRY(fresh.alloc(&nw, nn * kBrickVox));
+    TSDF_TRY(fresh.alloc(&nc, nn * kBrickVox));
+    TSDF_TRY(fresh.alloc(&no, nn * 8));
+    TSDF_TRY(fresh.alloc(&nf, nn));
     TSDF_HIP(hipMemcpyAsync(nt, B.pool.tsdf, old_n * kBrickVox * sizeof(float), hipMemcpyDeviceToDevice, B.stream));
     TSDF_HIP(hipMemcpyAsync(nw, B.pool.weight, old_n * kBrickVox * sizeof(float), hipMemcpyDeviceToDevice, B.stream));
     TSDF_HIP(hipMemcpyAsync(nc, B.pool.color, old_n * kBrickVox * sizeof(float), hipMemcpyDeviceToDevice, B.stream));
@@ -786,8 +763,8 @@ int resize_table(tsdf_hash* h, long long new_cap) {
     Table nt = h->t;
     nt.capacity = new_cap;
     DevBufs fresh;
-    TSDF_TRY(dev_alloc(fresh, &nt.keys, sizeof(unsigned long long) * new_cap));
-    TSDF_TRY(dev_alloc(fresh, &nt.vals, sizeof(int) * new_cap));
+    TSDF_TRY(fresh.alloc(&nt.keys, (size_t)new_cap));
+    TSDF_TRY(fresh.alloc(&nt.vals, (size_t)new_cap));
     hipLaunchKernelGGL(k_fill_keys, dim3(2048), dim3(256), 0, B.stream, nt.keys, nt.vals, (long long)new_cap);
     TSDF_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_rehash, dim3(2048), dim3(256), 0, B.stream, h->t, nt);
@@ -867,15 +844,14 @@ int table_room(tsdf_hash* h, long long live, long long extra, long long tombs, b
 
 int info_raw(tsdf_hash* h, InfoDev* out) {
     Base& B = h->b;
+    DevBufs bufs;
     InfoDev* d = nullptr;
-    TSDF_HIP(hipMalloc(&d, sizeof(InfoDev)));
+    TSDF_TRY(bufs.alloc(&d, 1));
     TSDF_HIP(hipMemsetAsync(d, 0, sizeof(InfoDev), B.stream));
     hipLaunchKernelGGL(k_info, dim3(2048), dim3(256), 0, B.stream, h->t, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(InfoDev), hipMemcpyDeviceToHost, B.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(B.stream);
-    (void)hipFree(d);
-    TSDF_HIP(e);
+    TSDF_HIP(hipGetLastError());
+    TSDF_HIP(hipMemcpyAsync(out, d, sizeof(InfoDev), hipMemcpyDeviceToHost, B.stream));
+    TSDF_HIP(hipStreamSynchronize(B.stream));
     return TSDF_OK;
 }
 
@@ -1257,10 +1233,11 @@ int hash_flush(tsdf_hash* h, bool wait = true) {
     return TSDF_OK;
 }
 
-int upload(tsdf_hash* h, const void* src, size_t bytes, void** dst) {
+// a host array into a device buffer of the call (*dst stays null for no array or an empty one)
+int upload(tsdf_hash* h, DevBufs& bufs, const void* src, size_t bytes, void** dst) {
     *dst = nullptr;
     if (!src || !bytes) return TSDF_OK;
-    TSDF_HIP(hipMalloc(dst, bytes));
+    TSDF_TRY(bufs.alloc(dst, bytes));
     TSDF_HIP(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, h->b.stream));
     return TSDF_OK;
 }
@@ -1268,8 +1245,8 @@ int upload(tsdf_hash* h, const void* src, size_t bytes, void** dst) {
 // Find-or-insert of distinct block keys (room first: the reference resizes before inserting,
 // hash_fusion.py:208-209); *dblk / *dslot: device arrays (owned by bufs) of each key's block and
 // slot.  Stream-ordered: the caller's kernels that use them follow on the handle's stream.
-int insert_block_keys(tsdf_hash* h, const std::vector<unsigned long long>& keys, DevBufs& bufs, void** dblk,
-                      void** dslot) {
+int insert_block_keys(tsdf_hash* h, const std::vector<unsigned long long>& keys, DevBufs& bufs, int** dblk,
+                      long long** dslot) {
     Base& B = h->b;
     const long long nk = (long long)keys.size();
     TSDF_TRY(read_state(h));
@@ -1279,15 +1256,12 @@ int insert_block_keys(tsdf_hash* h, const std::vector<unsigned long long>& keys,
     if (h->host_st.pool_top + nk > h->t.max_blocks - h->host_st.free_count)
         TSDF_TRY(grow_pool(h, pool_target(h, h->host_st.pool_top + 2 * nk)));
     void* dkeys;
-    TSDF_TRY(upload(h, keys.data(), sizeof(unsigned long long) * nk, &dkeys));
-    bufs.add(dkeys);
-    TSDF_HIP(hipMalloc(dblk, sizeof(int) * (nk ? nk : 1)));
-    bufs.add(*dblk);
-    TSDF_HIP(hipMalloc(dslot, sizeof(long long) * (nk ? nk : 1)));
-    bufs.add(*dslot);
+    TSDF_TRY(upload(h, bufs, keys.data(), sizeof(unsigned long long) * nk, &dkeys));
+    TSDF_TRY(bufs.alloc(dblk, (size_t)nk));
+    TSDF_TRY(bufs.alloc(dslot, (size_t)nk));
     if (nk == 0) return TSDF_OK;
     hipLaunchKernelGGL(k_insert_blocks, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, B.stream, h->t,
-                       B.pool, (const unsigned long long*)dkeys, (long long)nk, (int*)*dblk, (long long*)*dslot);
+                       B.pool, (const unsigned long long*)dkeys, (long long)nk, *dblk, *dslot);
     TSDF_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, B.stream, h->t.st, (long long)h->t.max_blocks,
                        (PoolReport*)nullptr, -1ll, (const unsigned*)nullptr);
@@ -1512,17 +1486,16 @@ int tsdf_hash_lookup(tsdf_hash_t* h, const int64_t* ijk, int64_t n, float* tsdf_
     TSDF_HIP(hipSetDevice(B.device));
     TSDF_TRY(hash_flush(h));
     DevBufs bufs;
-    void *dijk, *dt = nullptr, *dw = nullptr, *dc = nullptr, *df = nullptr;
-    TSDF_TRY(upload(h, ijk, sizeof(int64_t) * 3 * n, &dijk));
-    bufs.add(dijk);
-    if (tsdf_) { TSDF_HIP(hipMalloc(&dt, sizeof(float) * n)); bufs.add(dt); }
-    if (weight_) { TSDF_HIP(hipMalloc(&dw, sizeof(float) * n)); bufs.add(dw); }
-    if (color_) { TSDF_HIP(hipMalloc(&dc, sizeof(float) * n)); bufs.add(dc); }
-    TSDF_HIP(hipMalloc(&df, n));
-    bufs.add(df);
+    void* dijk;
+    float *dt = nullptr, *dw = nullptr, *dc = nullptr;
+    unsigned char* df = nullptr;
+    TSDF_TRY(upload(h, bufs, ijk, sizeof(int64_t) * 3 * n, &dijk));
+    if (tsdf_) TSDF_TRY(bufs.alloc(&dt, (size_t)n));
+    if (weight_) TSDF_TRY(bufs.alloc(&dw, (size_t)n));
+    if (color_) TSDF_TRY(bufs.alloc(&dc, (size_t)n));
+    TSDF_TRY(bufs.alloc(&df, (size_t)n));
     hipLaunchKernelGGL(k_lookup, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, B.stream, B.vol, h->t,
-                       B.pool, (const long long*)dijk, (long long)n, (float*)dt, (float*)dw, (float*)dc,
-                       (unsigned char*)df);
+                       B.pool, (const long long*)dijk, (long long)n, dt, dw, dc, df);
     TSDF_HIP(hipGetLastError());
     if (tsdf_) TSDF_HIP(hipMemcpyAsync(tsdf_, dt, sizeof(float) * n, hipMemcpyDeviceToHost, B.stream));
     if (weight_) TSDF_HIP(hipMemcpyAsync(weight_, dw, sizeof(float) * n, hipMemcpyDeviceToHost, B.stream));
@@ -1549,23 +1522,21 @@ int tsdf_hash_insert(tsdf_hash_t* h, const int64_t* ijk, int64_t n, const float*
     TSDF_TRY(hash_flush(h));
     std::vector<unsigned long long> keys = unique_blocks(v, ijk, n);
     const long long nk = (long long)keys.size();
+    std::vector<int> blk(nk);  // (read back: declared before the owner of what they are read from)
+    std::vector<long long> sl(nk);
     DevBufs bufs;
-    void *dblk = nullptr, *dslot = nullptr, *dijk, *dt, *dw, *dc;
+    int* dblk = nullptr;
+    long long* dslot = nullptr;
+    void *dijk, *dt, *dw, *dc;
     TSDF_TRY(insert_block_keys(h, keys, bufs, &dblk, &dslot));
-    TSDF_TRY(upload(h, ijk, sizeof(int64_t) * 3 * n, &dijk));
-    bufs.add(dijk);
-    TSDF_TRY(upload(h, tsdf_, tsdf_ ? sizeof(float) * n : 0, &dt));
-    bufs.add(dt);
-    TSDF_TRY(upload(h, weight_, weight_ ? sizeof(float) * n : 0, &dw));
-    bufs.add(dw);
-    TSDF_TRY(upload(h, color_, color_ ? sizeof(float) * n : 0, &dc));
-    bufs.add(dc);
+    TSDF_TRY(upload(h, bufs, ijk, sizeof(int64_t) * 3 * n, &dijk));
+    TSDF_TRY(upload(h, bufs, tsdf_, sizeof(float) * n, &dt));
+    TSDF_TRY(upload(h, bufs, weight_, sizeof(float) * n, &dw));
+    TSDF_TRY(upload(h, bufs, color_, sizeof(float) * n, &dc));
     hipLaunchKernelGGL(k_set_voxels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, B.stream, B.vol, h->t,
                        B.pool, (const long long*)dijk, (long long)n, (const float*)dt, (const float*)dw,
                        (const float*)dc);
     TSDF_HIP(hipGetLastError());
-    std::vector<int> blk(nk);
-    std::vector<long long> sl(nk);
     TSDF_HIP(hipMemcpyAsync(blk.data(), dblk, sizeof(int) * nk, hipMemcpyDeviceToHost, B.stream));
     TSDF_HIP(hipMemcpyAsync(sl.data(), dslot, sizeof(long long) * nk, hipMemcpyDeviceToHost, B.stream));
     TSDF_HIP(hipStreamSynchronize(B.stream));
@@ -1593,19 +1564,15 @@ int tsdf_hash_remove(tsdf_hash_t* h, const int64_t* ijk, int64_t n, uint8_t* rem
     TSDF_TRY(hash_flush(h));
     std::vector<unsigned long long> keys = unique_blocks(B.vol, ijk, n);
     DevBufs bufs;
-    void *dijk, *dkeys, *drem = nullptr;
-    TSDF_TRY(upload(h, ijk, sizeof(int64_t) * 3 * n, &dijk));
-    bufs.add(dijk);
-    if (removed) {
-        TSDF_HIP(hipMalloc(&drem, n));
-        bufs.add(drem);
-    }
+    void *dijk, *dkeys;
+    unsigned char* drem = nullptr;
+    TSDF_TRY(upload(h, bufs, ijk, sizeof(int64_t) * 3 * n, &dijk));
+    if (removed) TSDF_TRY(bufs.alloc(&drem, (size_t)n));
     hipLaunchKernelGGL(k_remove_voxels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, B.stream, B.vol,
-                       h->t, B.pool, (const long long*)dijk, (long long)n, (unsigned char*)drem);
+                       h->t, B.pool, (const long long*)dijk, (long long)n, drem);
     TSDF_HIP(hipGetLastError());
     if (!keys.empty()) {
-        TSDF_TRY(upload(h, keys.data(), sizeof(unsigned long long) * keys.size(), &dkeys));
-        bufs.add(dkeys);
+        TSDF_TRY(upload(h, bufs, keys.data(), sizeof(unsigned long long) * keys.size(), &dkeys));
         hipLaunchKernelGGL(k_free_empty, dim3((unsigned)((keys.size() + 255) / 256)), dim3(256), 0, B.stream,
                            h->t, (const unsigned long long*)dkeys, (long long)keys.size());
         TSDF_HIP(hipGetLastError());
@@ -1656,14 +1623,13 @@ int tsdf_hash_get_dense(tsdf_hash_t* h, float* tsdf_, float* weight_, float* col
     TSDF_TRY(hash_flush(h));
     const size_t n = (size_t)B.vol.dims[0] * B.vol.dims[1] * B.vol.dims[2];
     DevBufs bufs;
-    void *dt = nullptr, *dw = nullptr, *dc = nullptr;
-    if (tsdf_) { TSDF_HIP(hipMalloc(&dt, n * sizeof(float))); bufs.add(dt); }
-    if (weight_) { TSDF_HIP(hipMalloc(&dw, n * sizeof(float))); bufs.add(dw); }
-    if (color_) { TSDF_HIP(hipMalloc(&dc, n * sizeof(float))); bufs.add(dc); }
-    hipLaunchKernelGGL(k_fill_dense, dim3(4096), dim3(256), 0, B.stream, (float*)dt, (float*)dw, (float*)dc, n);
+    float *dt = nullptr, *dw = nullptr, *dc = nullptr;
+    if (tsdf_) TSDF_TRY(bufs.alloc(&dt, n));
+    if (weight_) TSDF_TRY(bufs.alloc(&dw, n));
+    if (color_) TSDF_TRY(bufs.alloc(&dc, n));
+    hipLaunchKernelGGL(k_fill_dense, dim3(4096), dim3(256), 0, B.stream, dt, dw, dc, n);
     TSDF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_to_dense, dim3(4096), dim3(256), 0, B.stream, B.vol, h->t, B.pool, (float*)dt,
-                       (float*)dw, (float*)dc);
+    hipLaunchKernelGGL(k_to_dense, dim3(4096), dim3(256), 0, B.stream, B.vol, h->t, B.pool, dt, dw, dc);
     TSDF_HIP(hipGetLastError());
     if (tsdf_) TSDF_HIP(hipMemcpyAsync(tsdf_, dt, n * sizeof(float), hipMemcpyDeviceToHost, B.stream));
     if (weight_) TSDF_HIP(hipMemcpyAsync(weight_, dw, n * sizeof(float), hipMemcpyDeviceToHost, B.stream));
@@ -1791,24 +1757,20 @@ int tsdf_hash_export_blocks(tsdf_hash_t* h, int32_t* bxyz, float* tsdf_, float* 
     }
     if (*n_blocks < live) return set_error(TSDF_E_ARG, "output holds %lld blocks, %lld live", (long long)*n_blocks, live);
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
+    unsigned long long got = 0;  // (read back: declared before the owner of what it is read from)
     DevBufs bufs;
     void* d[5] = {bxyz, tsdf_, weight_, color_, occ};
     const size_t sz[5] = {sizeof(int32_t) * 3, sizeof(float) * kBrickVox, sizeof(float) * kBrickVox,
                           sizeof(float) * kBrickVox, sizeof(uint64_t) * 8};
     if (!dev)
         for (int k = 0; k < 5; ++k)
-            if (d[k]) {
-                TSDF_HIP(hipMalloc(&d[k], sz[k] * (live ? live : 1)));
-                bufs.add(d[k]);
-            }
+            if (d[k]) TSDF_TRY(bufs.alloc(&d[k], sz[k] * live));
     unsigned long long* counter;
-    TSDF_HIP(hipMalloc(&counter, sizeof(unsigned long long)));
-    bufs.add(counter);
+    TSDF_TRY(bufs.alloc(&counter, 1));
     TSDF_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), B.stream));
     hipLaunchKernelGGL(k_export_blocks, dim3(2048), dim3(256), 0, B.stream, h->t, B.pool, counter, live, (int*)d[0],
                        (float*)d[1], (float*)d[2], (float*)d[3], (unsigned long long*)d[4]);
     TSDF_HIP(hipGetLastError());
-    unsigned long long got = 0;
     TSDF_HIP(hipMemcpyAsync(&got, counter, sizeof(got), hipMemcpyDeviceToHost, B.stream));
     if (!dev) {
         void* out[5] = {bxyz, tsdf_, weight_, color_, occ};
@@ -1849,8 +1811,10 @@ int tsdf_hash_import_blocks(tsdf_hash_t* h, const int32_t* bxyz, int64_t n_block
         std::sort(u.begin(), u.end());
         if (std::adjacent_find(u.begin(), u.end()) != u.end()) return set_error(TSDF_E_ARG, "duplicate block in import");
     }
+    std::vector<int> blk((size_t)n_blocks);  // (read back: declared before the owner of what it is read from)
     DevBufs bufs;
-    void *dblk = nullptr, *dslot = nullptr;
+    int* dblk = nullptr;
+    long long* dslot = nullptr;
     TSDF_TRY(insert_block_keys(h, keys, bufs, &dblk, &dslot));
     const void* in[4] = {tsdf_, weight_, color_, occ};
     const size_t sz[4] = {sizeof(float) * kBrickVox, sizeof(float) * kBrickVox, sizeof(float) * kBrickVox,
@@ -1861,15 +1825,13 @@ int tsdf_hash_import_blocks(tsdf_hash_t* h, const int32_t* bxyz, int64_t n_block
         if (dev) {
             d[k] = (void*)in[k];
         } else {
-            TSDF_TRY(upload(h, in[k], sz[k] * n_blocks, &d[k]));
-            bufs.add(d[k]);
+            TSDF_TRY(upload(h, bufs, in[k], sz[k] * n_blocks, &d[k]));
         }
     }
     hipLaunchKernelGGL(k_write_blocks, dim3(2048), dim3(256), 0, B.stream, h->t, B.pool, (const int*)dblk,
                        (long long)n_blocks, (const float*)d[0], (const float*)d[1], (const float*)d[2],
                        (const unsigned long long*)d[3]);
     TSDF_HIP(hipGetLastError());
-    std::vector<int> blk((size_t)n_blocks);
     TSDF_HIP(hipMemcpyAsync(blk.data(), dblk, sizeof(int) * n_blocks, hipMemcpyDeviceToHost, B.stream));
     TSDF_HIP(hipStreamSynchronize(B.stream));
     for (int64_t i = 0; i < n_blocks; ++i)

@@ -12,6 +12,7 @@
 #include "tsdf_device.h"
 #include "tsdf_hip.h"
 #include "tsdf_pipeline.h"
+#include "tsdf_scratch.h"
 
 #ifndef TSDF_CULL_WAVES_DEFAULT  // service waves per integrate workgroup where the rule applies (Base::cull_waves)
 #define TSDF_CULL_WAVES_DEFAULT 2
@@ -35,6 +36,45 @@ int set_error(int code, const char* fmt, ...);
         int r_ = (expr);          \
         if (r_ != TSDF_OK) return r_; \
     } while (0)
+
+// The device buffers of one call, freed together when the owner goes out of scope -- on every exit
+// path, and never between a call's stages (a free waits for the device) -- unless keep() hands
+// them on to a handle.  The free also waits for the call's asynchronous copies: a host array or
+// read-back target given to one is declared BEFORE the owner, so it outlives them on the error
+// paths too.  bytes: everything allocated.
+struct DevBufs {
+    std::vector<void*> p;
+    size_t bytes = 0;
+    DevBufs() = default;
+    DevBufs(const DevBufs&) = delete;
+    DevBufs& operator=(const DevBufs&) = delete;
+    ~DevBufs() {
+        for (void* q : p) (void)hipFree(q);
+    }
+    int alloc(void** out, size_t n_bytes) {  // (at least one byte: never a null pointer)
+        *out = nullptr;
+        n_bytes = n_bytes ? n_bytes : 1;
+        p.push_back(nullptr);
+        TSDF_HIP(hipMalloc(&p.back(), n_bytes));
+        *out = p.back();
+        bytes += n_bytes;
+        return TSDF_OK;
+    }
+    template <typename T>
+    int alloc(T** out, size_t n_elems) {
+        void* q = nullptr;
+        const int r = alloc(&q, sizeof(T) * n_elems);
+        *out = (T*)q;
+        return r;
+    }
+    int alloc(Layout& l) {  // one allocation for all of the layout's arrays
+        char* base = nullptr;
+        TSDF_TRY(alloc(&base, l.bytes()));
+        l.bind(base);
+        return TSDF_OK;
+    }
+    void keep() { p.clear(); }
+};
 
 inline size_t frame_bytes_depth(int dk, int H, int W) { return (size_t)H * W * (dk == TSDF_DEPTH_U16_MM ? 2 : 8); }
 inline size_t frame_bytes_color(int ck, int H, int W) { return (size_t)H * W * (ck == TSDF_COLOR_RGB8 ? 3 : 4); }
@@ -284,7 +324,19 @@ struct Mesh {
     int* faces = nullptr;             // n_tris x 3 vertex ids
     long long* keys = nullptr;        // n_verts global vertex keys ((x*Y + y)*Z + z)*3 + axis
     long long n_verts = 0, n_tris = 0;
+    // fresh arrays for nv vertices and nt triangles; fields: TSDF_MESH_NORMALS | TSDF_MESH_FACES,
+    // the arrays to have beside vertices, colours and keys
+    int alloc(long long nv, long long nt, int fields);
     void release();
+};
+// Releases the mesh unless the extraction reached its end.
+struct MeshGuard {
+    Mesh& m;
+    bool done = false;
+    explicit MeshGuard(Mesh& m_) : m(m_) {}
+    ~MeshGuard() {
+        if (!done) m.release();
+    }
 };
 // The global x rows marching cubes runs over for one shard (tsdf_mesh.hip, Grid).
 struct MeshDomain {

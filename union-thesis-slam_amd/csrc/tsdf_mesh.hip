@@ -6,7 +6,7 @@
 //   k_mc_classify  one thread per voxel (C-order): the voxel's three +axis grid edges that cross
 //                  0 (a vertex each) and, for voxels that anchor a cell, the cell's case and
 //                  triangle count;
-//   (exclusive scans of both counts: vertex and triangle offsets, in C-order)
+//   (exclusive scans of both counts: vertex and triangle offsets, in C-order, entry n the total)
 //   k_mc_vertices  one thread per voxel with crossings: vertex position (linear interpolation,
 //                  index space, then world = p * voxel_size + origin in f32 as NumPy does),
 //                  normal (interpolated central-difference gradient, pointing to positive tsdf)
@@ -18,6 +18,10 @@
 // The voxel hash has its own mesher over the table's live blocks (hash_extract_mesh, further
 // down): the same mesh as the dense passes give on the densified table, from the same device
 // functions (mc_edges, mc_case, mc_grad, mc_vertex), without a pass over the extent.
+// Host side, both meshers alike: a call's scratch is owned by one DevBufs (tsdf_host.h) and laid
+// out by a Layout (tsdf_scratch.h), one allocation per stage -- the dense mesher has one stage,
+// the hash's four -- freed together at the end of the call; the outputs are Mesh::alloc's, kept
+// only if the extraction reaches its end (MeshGuard); every HIP call returns through TSDF_HIP.
 #include <hipcub/hipcub.hpp>
 
 #include <cstring>
@@ -665,15 +669,34 @@ int bits_for(unsigned long long n) {  // radix-sort bits that hold every value <
     return b;
 }
 
-template <typename T>
-int dev_alloc(T** p, size_t n) {
-    TSDF_HIP(hipMalloc((void**)p, sizeof(T) * (n ? n : 1)));
+// the case table's triangle counts (256 bytes) and edge lists (4 KB) into the call's scratch
+int upload_table(unsigned char* ntri, signed char* tri, hipStream_t s) {
+    const McTable& tab = table();
+    TSDF_HIP(hipMemcpyAsync(ntri, tab.ntri, sizeof(tab.ntri), hipMemcpyHostToDevice, s));
+    TSDF_HIP(hipMemcpyAsync(tri, tab.tri, sizeof(tab.tri), hipMemcpyHostToDevice, s));
     return TSDF_OK;
 }
 
 }  // namespace
 
 namespace tsdf {
+
+int Mesh::alloc(long long nv, long long nt, int fields) {
+    release();
+    DevBufs fresh;  // freed again if an allocation fails
+    Mesh f;
+    const size_t v = (size_t)nv, t = (size_t)nt;
+    TSDF_TRY(fresh.alloc(&f.verts, 3 * v));
+    TSDF_TRY(fresh.alloc(&f.colors, 3 * v));
+    TSDF_TRY(fresh.alloc(&f.keys, v));
+    if (fields & TSDF_MESH_NORMALS) TSDF_TRY(fresh.alloc(&f.normals, 3 * v));
+    if (fields & TSDF_MESH_FACES) TSDF_TRY(fresh.alloc(&f.faces, 3 * t));
+    fresh.keep();
+    f.n_verts = nv;
+    f.n_tris = nt;
+    *this = f;
+    return TSDF_OK;
+}
 
 void Mesh::release() {
     for (void* p : {(void*)verts, (void*)normals, (void*)colors, (void*)faces, (void*)keys})
@@ -755,7 +778,6 @@ int mesh_halo_rows(const Vol& v, long long global_x, std::vector<long long>* out
 // and halo rows of `d` (halo rows: device C-order slices, nullptr when there are none).
 int extract_mesh(Base& B, const Pool& pool, Mesh& m, const MeshDomain& d, const float* ht, const float* hc) {
     m.release();
-    const McTable& tab = table();
     const int nrows = (int)d.vrow_gx.size();
     Grid g;
     g.Y = B.vol.dims[1];
@@ -770,111 +792,68 @@ int extract_mesh(Base& B, const Pool& pool, Mesh& m, const MeshDomain& d, const 
     g.hc = hc;
     const size_t n = (size_t)nrows * g.Y * g.Z;
     if (n >= (1ull << 31)) return set_error(TSDF_E_ARG, "volume too large for one mesh extraction (>= 2^31 voxels)");
+    if (n == 0) return TSDF_OK;  // (no vertex rows: the empty mesh)
     hipStream_t s = B.stream;
+    MeshGuard guard(m);
+    unsigned totals[2] = {0, 0};  // (read back: declared before the owner of what it is read from)
+    DevBufs sc;
+    // One allocation: per voxel the crossing bits, the case and both counts with their offsets
+    // (entry n of each scan is the total: n + 1 counts, the last one 0), then the tables, the
+    // domain's rows and the scan's temporary storage.  (n + 1 < 2^31: every dimension is at most
+    // 2^24, and 2^31 - 1 is prime.)
     unsigned char *ebits = nullptr, *cubes = nullptr, *ntri = nullptr, *vcap = nullptr;
     signed char* dtri = nullptr;
     unsigned *vcnt = nullptr, *tcnt = nullptr, *vbase = nullptr, *tbase = nullptr;
     int *rmap = nullptr, *vgx = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    int r = TSDF_OK;
-    auto cleanup = [&]() {
-        for (void* p : {(void*)ebits, (void*)cubes, (void*)ntri, (void*)dtri, (void*)vcnt, (void*)tcnt, (void*)vbase,
-                        (void*)tbase, (void*)rmap, (void*)vgx, (void*)vcap, tmp})
-            if (p) (void)hipFree(p);
-    };
-    do {
-        if ((r = dev_alloc(&ebits, n)) || (r = dev_alloc(&cubes, n)) || (r = dev_alloc(&ntri, 256)) ||
-            (r = dev_alloc(&dtri, 256 * 16)) || (r = dev_alloc(&vcnt, n)) || (r = dev_alloc(&tcnt, n)) ||
-            (r = dev_alloc(&vbase, n + 1)) || (r = dev_alloc(&tbase, n + 1)) ||
-            (r = dev_alloc(&rmap, d.row_map.size())) || (r = dev_alloc(&vgx, (size_t)nrows)) ||
-            (r = dev_alloc(&vcap, (size_t)nrows)))
-            break;
-        hipError_t e = hipMemcpyAsync(ntri, tab.ntri, 256, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(dtri, tab.tri, 256 * 16, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(rmap, d.row_map.data(), sizeof(int) * d.row_map.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && nrows) e = hipMemcpyAsync(vgx, d.vrow_gx.data(), sizeof(int) * nrows, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && nrows) e = hipMemcpyAsync(vcap, d.vrow_cap.data(), nrows, hipMemcpyHostToDevice, s);
-        g.row_map = rmap;
-        g.vrow_gx = vgx;
-        g.vrow_cap = vcap;
-        if (n == 0) {
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) r = set_error(TSDF_E_HIP, "mesh setup: %s", hipGetErrorString(e));
-            break;
-        }
-        const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)B.n_cu * 32);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_mc_classify, dim3(grid), dim3(256), 0, s, g, nrows, (const unsigned char*)ntri, ebits,
-                               cubes, vcnt, tcnt);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, vcnt, vbase, (int)n, s);
-        if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, vcnt, vbase, (int)n, s);
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, tcnt, tbase, (int)n, s);
-        unsigned last[4] = {0, 0, 0, 0};
-        if (e == hipSuccess) e = hipMemcpyAsync(&last[0], vbase + n - 1, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&last[1], vcnt + n - 1, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&last[2], tbase + n - 1, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&last[3], tcnt + n - 1, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            r = set_error(TSDF_E_HIP, "mesh classify/scan: %s", hipGetErrorString(e));
-            break;
-        }
-        m.n_verts = (long long)last[0] + last[1];
-        m.n_tris = (long long)last[2] + last[3];
-        if ((r = dev_alloc(&m.verts, 3 * m.n_verts)) || (r = dev_alloc(&m.normals, 3 * m.n_verts)) ||
-            (r = dev_alloc(&m.colors, 3 * m.n_verts)) || (r = dev_alloc(&m.faces, 3 * m.n_tris)) ||
-            (r = dev_alloc(&m.keys, m.n_verts)))
-            break;
-        hipLaunchKernelGGL(k_mc_vertices, dim3(grid), dim3(256), 0, s, g, nrows, (const unsigned char*)ebits,
-                           (const unsigned*)vbase, B.vol.origin[0], B.vol.origin[1], B.vol.origin[2],
-                           (float)B.vol.vs, m.verts, m.normals, m.colors, m.keys);
-        hipLaunchKernelGGL(k_mc_triangles, dim3(grid), dim3(256), 0, s, g, nrows, (const signed char*)dtri,
-                           (const unsigned char*)cubes, (const unsigned char*)ebits, (const unsigned*)vbase,
-                           (const unsigned*)tbase, m.faces);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) r = set_error(TSDF_E_HIP, "mesh emit: %s", hipGetErrorString(e));
-    } while (false);
-    cleanup();
-    if (r != TSDF_OK) m.release();
-    return r;
+    char* tmp = nullptr;
+    size_t need = 0;
+    TSDF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, vcnt, vbase, (int)(n + 1), s));
+    Layout l;
+    l.add(&ebits, n);
+    l.add(&cubes, n);
+    l.add(&vcnt, n + 1);
+    l.add(&tcnt, n + 1);
+    l.add(&vbase, n + 1);
+    l.add(&tbase, n + 1);
+    l.add(&ntri, 256);
+    l.add(&dtri, 256 * 16);
+    l.add(&rmap, d.row_map.size());
+    l.add(&vgx, (size_t)nrows);
+    l.add(&vcap, (size_t)nrows);
+    l.add(&tmp, need);
+    TSDF_TRY(sc.alloc(l));
+    TSDF_TRY(upload_table(ntri, dtri, s));
+    TSDF_HIP(hipMemcpyAsync(rmap, d.row_map.data(), sizeof(int) * d.row_map.size(), hipMemcpyHostToDevice, s));
+    TSDF_HIP(hipMemcpyAsync(vgx, d.vrow_gx.data(), sizeof(int) * nrows, hipMemcpyHostToDevice, s));
+    TSDF_HIP(hipMemcpyAsync(vcap, d.vrow_cap.data(), nrows, hipMemcpyHostToDevice, s));
+    TSDF_HIP(hipMemsetAsync(vcnt + n, 0, sizeof(unsigned), s));
+    TSDF_HIP(hipMemsetAsync(tcnt + n, 0, sizeof(unsigned), s));
+    g.row_map = rmap;
+    g.vrow_gx = vgx;
+    g.vrow_cap = vcap;
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)B.n_cu * 32);
+    hipLaunchKernelGGL(k_mc_classify, dim3(grid), dim3(256), 0, s, g, nrows, (const unsigned char*)ntri, ebits, cubes,
+                       vcnt, tcnt);
+    TSDF_HIP(hipGetLastError());
+    TSDF_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, need, vcnt, vbase, (int)(n + 1), s));
+    TSDF_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, need, tcnt, tbase, (int)(n + 1), s));
+    TSDF_HIP(hipMemcpyAsync(&totals[0], vbase + n, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    TSDF_HIP(hipMemcpyAsync(&totals[1], tbase + n, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    TSDF_HIP(hipStreamSynchronize(s));
+    TSDF_TRY(m.alloc(totals[0], totals[1], TSDF_MESH_NORMALS | TSDF_MESH_FACES));
+    hipLaunchKernelGGL(k_mc_vertices, dim3(grid), dim3(256), 0, s, g, nrows, (const unsigned char*)ebits,
+                       (const unsigned*)vbase, B.vol.origin[0], B.vol.origin[1], B.vol.origin[2], (float)B.vol.vs,
+                       m.verts, m.normals, m.colors, m.keys);
+    hipLaunchKernelGGL(k_mc_triangles, dim3(grid), dim3(256), 0, s, g, nrows, (const signed char*)dtri,
+                       (const unsigned char*)cubes, (const unsigned char*)ebits, (const unsigned*)vbase,
+                       (const unsigned*)tbase, m.faces);
+    TSDF_HIP(hipGetLastError());
+    TSDF_HIP(hipStreamSynchronize(s));
+    guard.done = true;
+    return TSDF_OK;
 }
 
 namespace {
-
-// Device buffers of one hash extraction, freed together at its end (a free in between would wait
-// for the stream); bytes: everything allocated, the scratch_bytes of tsdf_hash_mesh_info.  One
-// allocation per stage (an allocation costs the host more than any of the stages' kernels): a
-// stage lays its arrays out twice with a Carver, first without memory for the size, then in it.
-struct Scratch {
-    std::vector<void*> p;
-    size_t bytes = 0;
-    ~Scratch() {
-        for (void* q : p) (void)hipFree(q);
-    }
-    int get(char** out, size_t b) {
-        *out = nullptr;
-        b = b ? b : 1;
-        TSDF_HIP(hipMalloc((void**)out, b));
-        p.push_back(*out);
-        bytes += b;
-        return TSDF_OK;
-    }
-};
-struct Carver {
-    char* base = nullptr;
-    size_t off = 0;
-    template <typename T>
-    T* take(size_t n) {
-        const size_t o = off;
-        off += (sizeof(T) * n + 255) & ~(size_t)255;
-        return base ? (T*)(base + o) : nullptr;
-    }
-};
 
 unsigned flat_grid(const Base& B, long long n) {
     return (unsigned)std::max<long long>(1, std::min<long long>((n + 255) / 256, (long long)B.n_cu * 32));
@@ -887,11 +866,14 @@ unsigned flat_grid(const Base& B, long long n) {
 // by the volume's extent: the passes walk the table's slots, the live blocks, the mesh blocks and
 // the mesh.  fields: TSDF_MESH_NORMALS | TSDF_MESH_FACES, what to extract beside vertices, colours
 // and keys (the triangle count is given either way).
+// One allocation per stage (an allocation costs the host more than any of the stages' kernels): a
+// stage records its arrays in a Layout and the call's DevBufs allocates them together; all of
+// them are freed at the end of the call.  scratch_bytes of tsdf_hash_mesh_info: everything
+// allocated, the mesh included.
 int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_mesh_info_t* info) {
     m.release();
     *info = tsdf_hash_mesh_info_t{};
     const bool want_n = (fields & TSDF_MESH_NORMALS) != 0, want_f = (fields & TSDF_MESH_FACES) != 0;
-    const McTable& tab = table();
     hipStream_t s = B.stream;
     HashMeshArgs a;
     a.g.X = B.vol.dims[0], a.g.Y = B.vol.dims[1], a.g.Z = B.vol.dims[2];
@@ -900,36 +882,32 @@ int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_me
     a.pool = B.pool;
     const unsigned long long n_blocks = (unsigned long long)a.g.nbx * a.g.nby * a.g.nbz;  // also the `none` candidate
     const unsigned long long n_vox = (unsigned long long)a.g.X * a.g.Y * a.g.Z;
-    Scratch sc;
+    MeshGuard guard(m);
+    // (read back: declared before the owner of what they are read from)
+    unsigned long long n_live_u = 0, totals[2] = {0, 0};
+    long long n_mesh = 0;
+    DevBufs sc;
     // 1. the live blocks' coordinates
     unsigned long long* counters = nullptr;  // [0] live blocks, [1] the list's cursor, [2] mesh blocks
     unsigned char* ntri = nullptr;
     signed char* dtri = nullptr;
-    {
-        Carver c;
-        for (int pass = 0; pass < 2; ++pass) {
-            c.off = 0;
-            counters = c.take<unsigned long long>(4);
-            ntri = c.take<unsigned char>(256);
-            dtri = c.take<signed char>(256 * 16);
-            if (pass == 0) TSDF_TRY(sc.get(&c.base, c.off));
-        }
-    }
+    Layout l1;
+    l1.add(&counters, 4);
+    l1.add(&ntri, 256);
+    l1.add(&dtri, 256 * 16);
+    TSDF_TRY(sc.alloc(l1));
     TSDF_HIP(hipMemsetAsync(counters, 0, sizeof(unsigned long long) * 4, s));
-    TSDF_HIP(hipMemcpyAsync(ntri, tab.ntri, 256, hipMemcpyHostToDevice, s));
-    TSDF_HIP(hipMemcpyAsync(dtri, tab.tri, 256 * 16, hipMemcpyHostToDevice, s));
+    TSDF_TRY(upload_table(ntri, dtri, s));
     const unsigned slot_grid =
         (unsigned)std::max<long long>(1, std::min<long long>((t.capacity + 256 * kSlotsPerLane - 1) / (256 * kSlotsPerLane), 1024));
     hipLaunchKernelGGL(k_hm_live, dim3(slot_grid), dim3(256), 0, s, a.g, t, counters, 0ll, (unsigned long long*)nullptr);
     TSDF_HIP(hipGetLastError());
-    unsigned long long n_live_u = 0;
     TSDF_HIP(hipMemcpyAsync(&n_live_u, counters, sizeof(n_live_u), hipMemcpyDeviceToHost, s));
     TSDF_HIP(hipStreamSynchronize(s));
     const long long n_live = (long long)n_live_u;
     info->live_blocks = n_live;
     if (n_live >= (1ll << 28)) return set_error(TSDF_E_ARG, "too many live blocks for one mesh extraction (%lld)", n_live);
     // 2. the mesh blocks: the live blocks' -neighbourhoods, sorted, each once
-    long long n_mesh = 0;
     unsigned long long* mesh_blocks = nullptr;
     if (n_live > 0) {
         const int nc = (int)(8 * n_live), bb = bits_for(n_blocks + 1);
@@ -939,16 +917,13 @@ int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_me
         TSDF_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need_sort, cand, cand_s, nc, 0, bb, s));
         TSDF_HIP(hipcub::DeviceSelect::Unique(nullptr, need_uniq, cand_s, mesh_blocks, d_n_mesh, nc, s));
         char* tmp = nullptr;
-        Carver c;
-        for (int pass = 0; pass < 2; ++pass) {
-            c.off = 0;
-            live = c.take<unsigned long long>(n_live);
-            cand = c.take<unsigned long long>(nc);
-            cand_s = c.take<unsigned long long>(nc);
-            mesh_blocks = c.take<unsigned long long>(nc);
-            tmp = c.take<char>(std::max(need_sort, need_uniq));
-            if (pass == 0) TSDF_TRY(sc.get(&c.base, c.off));
-        }
+        Layout l;
+        l.add(&live, (size_t)n_live);
+        l.add(&cand, (size_t)nc);
+        l.add(&cand_s, (size_t)nc);
+        l.add(&mesh_blocks, (size_t)nc);
+        l.add(&tmp, std::max(need_sort, need_uniq));
+        TSDF_TRY(sc.alloc(l));
         hipLaunchKernelGGL(k_hm_live, dim3(slot_grid), dim3(256), 0, s, a.g, t, counters + 1, n_live, live);
         TSDF_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_hm_candidates, dim3(flat_grid(B, nc)), dim3(256), 0, s, a.g,
@@ -967,23 +942,19 @@ int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_me
     // 3. classify, and the blocks' offsets (entry n_mesh of each scan: the total)
     unsigned char *ebits = nullptr, *cubes = nullptr;
     unsigned long long *vcnt = nullptr, *tcnt = nullptr, *vbase = nullptr, *tbase = nullptr;
-    unsigned long long totals[2] = {0, 0};
     if (n_mesh > 0) {
         size_t need = 0;
         TSDF_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, vcnt, vbase, (int)(n_mesh + 1), s));
         char* tmp = nullptr;
-        Carver c;
-        for (int pass = 0; pass < 2; ++pass) {
-            c.off = 0;
-            ebits = c.take<unsigned char>((size_t)n_mesh * kBrickVox);
-            cubes = c.take<unsigned char>((size_t)n_mesh * kBrickVox);
-            vcnt = c.take<unsigned long long>(n_mesh + 1);
-            tcnt = c.take<unsigned long long>(n_mesh + 1);
-            vbase = c.take<unsigned long long>(n_mesh + 1);
-            tbase = c.take<unsigned long long>(n_mesh + 1);
-            tmp = c.take<char>(need);
-            if (pass == 0) TSDF_TRY(sc.get(&c.base, c.off));
-        }
+        Layout l;
+        l.add(&ebits, (size_t)n_mesh * kBrickVox);
+        l.add(&cubes, (size_t)n_mesh * kBrickVox);
+        l.add(&vcnt, (size_t)n_mesh + 1);
+        l.add(&tcnt, (size_t)n_mesh + 1);
+        l.add(&vbase, (size_t)n_mesh + 1);
+        l.add(&tbase, (size_t)n_mesh + 1);
+        l.add(&tmp, need);
+        TSDF_TRY(sc.alloc(l));
         TSDF_HIP(hipMemsetAsync(vcnt + n_mesh, 0, sizeof(unsigned long long), s));
         TSDF_HIP(hipMemsetAsync(tcnt + n_mesh, 0, sizeof(unsigned long long), s));
         hipLaunchKernelGGL(k_hm_classify, dim3((unsigned)n_mesh), dim3(256), 0, s, a, (const unsigned char*)ntri, ebits,
@@ -999,14 +970,9 @@ int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_me
         return set_error(TSDF_E_ARG, "mesh too large for int32 faces (%llu vertices, %llu triangles)", totals[0], totals[1]);
     const long long nv = (long long)totals[0], nt = (long long)totals[1];
     // 4. emit block by block, 5. into the global order.  The outputs belong to the mesh.
-    int r = TSDF_OK;
-    do {
-        if ((r = dev_alloc(&m.verts, 3 * (size_t)nv)) || (r = dev_alloc(&m.colors, 3 * (size_t)nv)) ||
-            (r = dev_alloc(&m.keys, (size_t)nv)) || (want_n && (r = dev_alloc(&m.normals, 3 * (size_t)nv))) ||
-            (want_f && (r = dev_alloc(&m.faces, 3 * (size_t)nt))))
-            break;
-        sc.bytes += (size_t)nv * (12 + 3 + 8 + (want_n ? 12 : 0)) + (want_f ? (size_t)nt * 12 : 0);
-        if (nv == 0) break;
+    TSDF_TRY(m.alloc(nv, nt, fields));
+    const size_t out_bytes = (size_t)nv * (12 + 3 + 8 + (want_n ? 12 : 0)) + (want_f ? (size_t)nt * 12 : 0);
+    if (nv > 0) {
         const bool tris = want_f && nt > 0;
         const int kb = bits_for(n_vox * 3), cb = bits_for(n_vox * 8);
         float *vu = nullptr, *nu = nullptr;
@@ -1015,64 +981,46 @@ int hash_extract_mesh(Base& B, const Table& t, Mesh& m, int fields, tsdf_hash_me
         unsigned *vi = nullptr, *vperm = nullptr, *ti = nullptr, *tperm = nullptr;
         unsigned long long *tk = nullptr, *tk_s = nullptr;
         size_t need_v = 0, need_t = 0;
-        hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, ku, m.keys, vi, vperm, (int)nv, 0, kb, s);
-        if (e == hipSuccess && tris)
-            e = hipcub::DeviceRadixSort::SortPairs(nullptr, need_t, tk, tk_s, ti, tperm, (int)nt, 0, cb, s);
+        TSDF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need_v, ku, m.keys, vi, vperm, (int)nv, 0, kb, s));
+        if (tris) TSDF_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need_t, tk, tk_s, ti, tperm, (int)nt, 0, cb, s));
         char* tmp = nullptr;
-        Carver c;
-        for (int pass = 0; pass < 2 && r == TSDF_OK; ++pass) {
-            c.off = 0;
-            vu = c.take<float>(3 * (size_t)nv);
-            cu = c.take<unsigned char>(3 * (size_t)nv);
-            ku = c.take<long long>((size_t)nv);
-            vi = c.take<unsigned>((size_t)nv);
-            vperm = c.take<unsigned>((size_t)nv);
-            if (want_n) nu = c.take<float>(3 * (size_t)nv);
-            if (tris) {
-                fkeys = c.take<long long>(3 * (size_t)nt);
-                tk = c.take<unsigned long long>((size_t)nt);
-                tk_s = c.take<unsigned long long>((size_t)nt);
-                ti = c.take<unsigned>((size_t)nt);
-                tperm = c.take<unsigned>((size_t)nt);
-            }
-            tmp = c.take<char>(std::max(need_v, need_t));
-            if (pass == 0) r = sc.get(&c.base, c.off);
+        Layout l;
+        l.add(&vu, 3 * (size_t)nv);
+        l.add(&cu, 3 * (size_t)nv);
+        l.add(&ku, (size_t)nv);
+        l.add(&vi, (size_t)nv);
+        l.add(&vperm, (size_t)nv);
+        if (want_n) l.add(&nu, 3 * (size_t)nv);
+        if (tris) {
+            l.add(&fkeys, 3 * (size_t)nt);
+            l.add(&tk, (size_t)nt);
+            l.add(&tk_s, (size_t)nt);
+            l.add(&ti, (size_t)nt);
+            l.add(&tperm, (size_t)nt);
         }
-        if (r != TSDF_OK) break;
-        if (e == hipSuccess) {
-            auto emit = want_n ? (tris ? k_hm_emit<true, true> : k_hm_emit<true, false>)
-                               : (tris ? k_hm_emit<false, true> : k_hm_emit<false, false>);
-            hipLaunchKernelGGL(emit, dim3((unsigned)n_mesh), dim3(256), 0, s, a, (const signed char*)dtri,
-                               (const unsigned char*)ebits, (const unsigned char*)cubes,
-                               (const unsigned long long*)vbase, (const unsigned long long*)tbase, B.vol.origin[0],
-                               B.vol.origin[1], B.vol.origin[2], (float)B.vol.vs, vu, nu, cu, ku, vi, tk, ti, fkeys);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, need_v, ku, m.keys, vi, vperm, (int)nv, 0, kb, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_hm_permute, dim3(flat_grid(B, nv)), dim3(256), 0, s, (const unsigned*)vperm, nv,
-                               (const float*)vu, (const float*)nu, (const unsigned char*)cu, m.verts, m.normals,
-                               m.colors);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && tris)
-            e = hipcub::DeviceRadixSort::SortPairs(tmp, need_t, tk, tk_s, ti, tperm, (int)nt, 0, cb, s);
-        if (e == hipSuccess && tris) {
+        l.add(&tmp, std::max(need_v, need_t));
+        TSDF_TRY(sc.alloc(l));
+        auto emit = want_n ? (tris ? k_hm_emit<true, true> : k_hm_emit<true, false>)
+                           : (tris ? k_hm_emit<false, true> : k_hm_emit<false, false>);
+        hipLaunchKernelGGL(emit, dim3((unsigned)n_mesh), dim3(256), 0, s, a, (const signed char*)dtri,
+                           (const unsigned char*)ebits, (const unsigned char*)cubes, (const unsigned long long*)vbase,
+                           (const unsigned long long*)tbase, B.vol.origin[0], B.vol.origin[1], B.vol.origin[2],
+                           (float)B.vol.vs, vu, nu, cu, ku, vi, tk, ti, fkeys);
+        TSDF_HIP(hipGetLastError());
+        TSDF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, need_v, ku, m.keys, vi, vperm, (int)nv, 0, kb, s));
+        hipLaunchKernelGGL(k_hm_permute, dim3(flat_grid(B, nv)), dim3(256), 0, s, (const unsigned*)vperm, nv,
+                           (const float*)vu, (const float*)nu, (const unsigned char*)cu, m.verts, m.normals, m.colors);
+        TSDF_HIP(hipGetLastError());
+        if (tris) {
+            TSDF_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, need_t, tk, tk_s, ti, tperm, (int)nt, 0, cb, s));
             hipLaunchKernelGGL(k_hm_faces, dim3(flat_grid(B, 3 * nt)), dim3(256), 0, s, (const unsigned*)tperm, nt,
                                (const long long*)fkeys, (const long long*)m.keys, nv, m.faces);
-            e = hipGetLastError();
+            TSDF_HIP(hipGetLastError());
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess)
-            r = set_error(e == hipErrorOutOfMemory ? TSDF_E_OOM : TSDF_E_HIP, "hash mesh emit: %s", hipGetErrorString(e));
-    } while (false);
-    if (r != TSDF_OK) {
-        m.release();
-        return r;
+        TSDF_HIP(hipStreamSynchronize(s));
     }
-    m.n_verts = nv;
-    m.n_tris = nt;
-    info->scratch_bytes = (int64_t)sc.bytes;
+    guard.done = true;
+    info->scratch_bytes = (int64_t)(sc.bytes + out_bytes);
     info->n_verts = nv;
     info->n_tris = nt;
     return TSDF_OK;
