@@ -571,6 +571,54 @@ int tsdf_icp_linearize_rgbd(int device, const void* depth, int depth_kind, const
                             int64_t counts[4], uint8_t* code, float* residual, uint8_t* color_code,
                             float* color_residual, int flags);
 
+/* ---- merge ------------------------------------------------------------------
+ * What a merge did to the destination. */
+typedef struct {
+    int64_t samples;          /* destination voxels that received a sample */
+    int64_t bricks_updated;   /* destination bricks / blocks with >= 1 sample */
+    int64_t blocks_allocated; /* hash destination: blocks newly allocated (0 for dense) */
+} tsdf_merge_info_t;
+
+/* Merge a fused volume (the source: src_dense or src_hash, exactly one non-NULL) into dst under
+ * src_to_dst, a rigid 4x4 row-major matrix taking source world coordinates to destination world
+ * coordinates.  Every destination voxel is taken to the source's index space, q = A (x, y, z) + b
+ * with A = R^T vs_D / vs_S and b = (R^T (o_D - t) - o_S) / vs_S rounded to f32 once; the source is
+ * sampled trilinearly in its cell floor(q) -- an axis with an exactly zero fraction neither fetches
+ * nor requires its upper neighbour -- and no sample is taken where the cell leaves the source or a
+ * corner that counts has weight <= 0 (a hash voxel without an entry: weight 0).  A sample blends
+ * u = clamp(trunc_S / trunc_D * v, -1, 1) with the weight w_S = the least corner weight, and the
+ * colour of the nearest corner, into the voxel by the integrate's exact update: w_N = w_D + w_S,
+ * t_N = f32((f64(w_D t_D) + f64(w_S u)) / f64(w_N)), colour channels min(255, rint((w_D old +
+ * w_S new) / w_N)).  A voxel without a sample keeps its bytes.  Every operation is a separately
+ * rounded f32 operation in the fixed order of §7h (restated by tests/merge_ref.py); the same inputs
+ * give the same bytes (no floating-point atomics).  Integer weights and canonical colours stay so;
+ * a translation by whole voxels between equal lattices copies every observed voxel bit for bit.
+ * A hash destination receives an entry for every sampled voxel and blocks for exactly the bricks
+ * with a sample; table and pool grow as tsdf_hash_import_blocks grows them.  Deferred frames of both
+ * handles run first, the source's stream is complete before the destination reads it, and the call
+ * is synchronous.  Frame statistics do not change.  info may be NULL; flags must be 0.
+ * TSDF_E_ARG: a NULL handle or matrix, both or neither source, the same handle on both sides,
+ * handles on different devices, a cyclic column shard or a hash shard (n_shards > 1) on either side
+ * (slab shards -- index_offset -- are accepted and use global indices), a matrix with an entry that
+ * is not finite, a last row other than 0 0 0 1 or a rotation not orthonormal with determinant +1 to
+ * 1e-6, and a source truncation below the destination's (no downsampling).  The destination is
+ * unchanged after a refusal.  TSDF_E_CAPACITY / TSDF_E_OOM (a hash destination whose table or pool
+ * could not grow): no voxel has changed, but blocks inserted before the failure stay in the table
+ * without entries, as after a failed tsdf_hash_import_blocks. */
+int tsdf_dense_merge(tsdf_dense_t* dst, tsdf_dense_t* src_dense, tsdf_hash_t* src_hash,
+                     const double src_to_dst[16], tsdf_merge_info_t* info, int flags);
+int tsdf_hash_merge(tsdf_hash_t* dst, tsdf_dense_t* src_dense, tsdf_hash_t* src_hash,
+                    const double src_to_dst[16], tsdf_merge_info_t* info, int flags);
+/* (As tsdf_raycast_last_ms and tsdf_track_last_ms: what a timing record of this path needs and a
+ * caller cannot get from outside -- the launches' device time apart from the host work between
+ * them, and what the cull skipped.)  The calling thread's last merge: the HIP-event time, in milliseconds, of its launches when the
+ * destination had profiling on (tsdf_*_set_profiling; a hash destination: the marking pass and the
+ * pass over the marked blocks, not the block insertion between them; -1 before any such call), and
+ * the destination bricks the cull let through -- those whose box, taken to the source's index space,
+ * can hold a cell inside the source that starts in a source brick with an observed voxel -- against
+ * info's bricks_updated (-1 before any merge). */
+int tsdf_merge_last_profile(double* ms, int64_t* candidate_bricks);
+
 /* hash_function over n coordinate triples (host in, host out), computed on the device.  The
  * same arithmetic as the kernels' home-slot computation. */
 int tsdf_hash_keys(const int64_t* xyz, int64_t n, int64_t table_size, int int_bits,

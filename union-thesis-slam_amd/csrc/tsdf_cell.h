@@ -37,6 +37,70 @@ __device__ inline void hash_block_voxel(const Table& tb, const Pool& pool, int b
     }
 }
 
+// ---- the cell of a handle's volume: what the tracker (tsdf_track.hip), the sampler and the merge
+// (tsdf_merge.hip) read it through ------------------------------------------------------------------
+struct SdfArgs {
+    Vol v;
+    Pool pool;
+    Table t;             // hash only
+    int hash;
+    float Qr[9], Qo[3];  // the guess camera's frame to index space: R_G / vs, (t_G - origin) / vs
+    float sc, trunc;     // trunc / vs (tsdf per voxel to metres per metre), trunc
+};
+
+// The cell at local index l (corners l + {0,1}^3, c[dx*4 + dy*2 + dz]) and its code: 2, 3, 4 or 6; c
+// is filled for 4 and 6.  Dense: the 16 gathers are issued together.  Hash: a cell touches 1, 2, 4
+// or 8 blocks ((l & 7) == 7 on an axis crosses to the next); each distinct block is probed once.
+// NK (the merge): n[k] = 0 marks a degenerate axis -- its upper neighbour has trilinear
+// weight zero and is neither fetched nor required, both corners are the voxel l[k]; w_out / blk_out:
+// the corners' weights and (hash) pool blocks.  Without NK none of the three is read or written.
+template <bool HASH, bool NK = false>
+__device__ inline int sdf_cell(const SdfArgs& x, const int l[3], float c[8], const int* n = nullptr, float* w_out = nullptr,
+                            int* blk_out = nullptr) {
+    for (int d = 0; d < 3; ++d)
+        if (l[d] < 0 || l[d] > x.v.dims[d] - (NK ? 1 + n[d] : 2)) return 2;
+    float w[8];
+    if (HASH) {
+        const bool cr[3] = {(!NK || n[0]) && (l[0] & 7) == 7, (!NK || n[1]) && (l[1] & 7) == 7, (!NK || n[2]) && (l[2] & 7) == 7};
+        int blk[8];  // the pool block of corner s
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int ox = s >> 2, oy = (s >> 1) & 1, oz = s & 1;
+            if (ox && !cr[0]) blk[s] = blk[s & 3];
+            else if (oy && !cr[1]) blk[s] = blk[s & 5];
+            else if (oz && !cr[2]) blk[s] = blk[s & 6];
+            else {
+                const int bx = (l[0] >> 3) + ox, by = (l[1] >> 3) + oy, bz = (l[2] >> 3) + oz;
+                blk[s] = bx < x.v.nb[0] && by < x.v.nb[1] && bz < x.v.nb[2] ? hash_find(x.t, bx, by, bz, x.t.max_blocks) : -1;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 8; ++s)
+            hash_block_voxel<false>(x.t, x.pool, blk[s], l[0] + (NK ? (s >> 2) * n[0] : (s >> 2)), l[1] + (NK ? ((s >> 1) & 1) * n[1] : ((s >> 1) & 1)),
+                                    l[2] + (NK ? (s & 1) * n[2] : (s & 1)), &c[s], &w[s]);
+        if (NK) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) blk_out[s] = blk[s];
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const size_t j = dense_index(x.v, l[0] + (NK ? (s >> 2) * n[0] : (s >> 2)), l[1] + (NK ? ((s >> 1) & 1) * n[1] : ((s >> 1) & 1)),
+                                          l[2] + (NK ? (s & 1) * n[2] : (s & 1)));
+            c[s] = x.pool.tsdf[j];
+            w[s] = x.pool.weight[j];
+        }
+    }
+    bool seen = true, flat = false;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        seen = seen && w[s] > 0.0f;
+        flat = flat || fabsf(c[s]) >= 1.0f;
+        if (NK) w_out[s] = w[s];
+    }
+    return !seen ? 3 : flat ? 4 : 6;
+}
+
 // lerp_z, then lerp_y, then lerp_x
 __device__ inline float trilinear(const float c[8], const float t[3]) {
     const float c00 = lerp(c[0], c[1], t[2]), c01 = lerp(c[2], c[3], t[2]);

@@ -1285,6 +1285,15 @@ std::vector<unsigned long long> unique_blocks(const Vol& v, const int64_t* ijk, 
 
 }  // namespace
 
+Base* tsdf::hash_base(tsdf_hash_t* h) { return &h->b; }
+
+int tsdf::hash_find_or_insert_blocks(tsdf_hash_t* h, const std::vector<unsigned long long>& keys, DevBufs& bufs, int** dblk) {
+    long long* dslot = nullptr;
+    return insert_block_keys(h, keys, bufs, dblk, &dslot);
+}
+
+int tsdf::hash_recheck_canon(tsdf_hash_t* h) { return recheck_canon(h); }
+
 int tsdf::hash_ray_source(tsdf_hash_t* h, RaySource* out) {
     Base& B = h->b;
     TSDF_HIP(hipSetDevice(B.device));

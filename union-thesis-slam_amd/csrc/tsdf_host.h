@@ -367,6 +367,13 @@ struct RaySource {
 int dense_ray_source(tsdf_dense_t* h, RaySource* out);
 int hash_ray_source(tsdf_hash_t* h, RaySource* out);
 
+// The merge's access to a hash destination (tsdf_merge.hip): the handle's state, the
+// find-or-insert of distinct block keys with the table's room and growth rules (*dblk: each key's pool
+// block, a device array owned by bufs; stream-ordered), and Vol::canon from the pool.
+Base* hash_base(tsdf_hash_t* h);
+int hash_find_or_insert_blocks(tsdf_hash_t* h, const std::vector<unsigned long long>& keys, DevBufs& bufs, int** dblk);
+int hash_recheck_canon(tsdf_hash_t* h);
+
 // Texels (Base::texel_now) for the batches one fused call prepares.
 struct TexelScope {
     Base& b;

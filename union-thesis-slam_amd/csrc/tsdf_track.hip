@@ -391,57 +391,6 @@ __global__ __launch_bounds__(kIcpWG) void k_icp_linearize(IcpArgs a) {
 //   0 not sampled / no depth     2 the cell is not inside the volume     3 a corner has weight <= 0
 //   4 a corner lies on the truncated plateau (|tsdf| >= 1)     5 |r| > dist_max or a zero gradient
 //   6 inlier
-struct SdfArgs {
-    Vol v;
-    Pool pool;
-    Table t;             // hash only
-    int hash;
-    float Qr[9], Qo[3];  // the guess camera's frame to index space: R_G / vs, (t_G - origin) / vs
-    float sc, trunc;     // trunc / vs (tsdf per voxel to metres per metre), trunc
-};
-
-// The cell at local index l (corners l + {0,1}^3, c[dx*4 + dy*2 + dz]) and its code: 2, 3, 4 or 6; c
-// is filled for 4 and 6.  Dense: the 16 gathers are issued together.  Hash: a cell touches 1, 2, 4
-// or 8 blocks ((l & 7) == 7 on an axis crosses to the next); each distinct block is probed once.
-template <bool HASH>
-__device__ inline int sdf_cell(const SdfArgs& x, const int l[3], float c[8]) {
-    for (int d = 0; d < 3; ++d)
-        if (l[d] < 0 || l[d] > x.v.dims[d] - 2) return 2;
-    float w[8];
-    if (HASH) {
-        const bool cr[3] = {(l[0] & 7) == 7, (l[1] & 7) == 7, (l[2] & 7) == 7};
-        int blk[8];  // the pool block of corner s
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int ox = s >> 2, oy = (s >> 1) & 1, oz = s & 1;
-            if (ox && !cr[0]) blk[s] = blk[s & 3];
-            else if (oy && !cr[1]) blk[s] = blk[s & 5];
-            else if (oz && !cr[2]) blk[s] = blk[s & 6];
-            else {
-                const int bx = (l[0] >> 3) + ox, by = (l[1] >> 3) + oy, bz = (l[2] >> 3) + oz;
-                blk[s] = bx < x.v.nb[0] && by < x.v.nb[1] && bz < x.v.nb[2] ? hash_find(x.t, bx, by, bz, x.t.max_blocks) : -1;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-            hash_block_voxel<false>(x.t, x.pool, blk[s], l[0] + (s >> 2), l[1] + ((s >> 1) & 1), l[2] + (s & 1), &c[s], &w[s]);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const size_t j = dense_index(x.v, l[0] + (s >> 2), l[1] + ((s >> 1) & 1), l[2] + (s & 1));
-            c[s] = x.pool.tsdf[j];
-            w[s] = x.pool.weight[j];
-        }
-    }
-    bool seen = true, flat = false;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        seen = seen && w[s] > 0.0f;
-        flat = flat || fabsf(c[s]) >= 1.0f;
-    }
-    return !seen ? 3 : flat ? 4 : 6;
-}
-
 // One lane per sampled pixel over k_icp_linearize's launch shape, feeding k_icp_finish<false>.
 template <int DK, bool HASH>
 __global__ __launch_bounds__(kIcpWG) void k_sdf_linearize(IcpArgs a, SdfArgs x) {

@@ -100,6 +100,14 @@ class TrackColorInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class MergeInfo(ctypes.Structure):
+    """tsdf_merge_info_t"""
+    _fields_ = [("samples", ctypes.c_int64), ("bricks_updated", ctypes.c_int64), ("blocks_allocated", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ICP_MAX_ITER = 64
 TRACK_STATUS = {1: "converged", 2: "max_iter", 3: "lost"}
 
@@ -173,6 +181,9 @@ SIGNATURES = {
     "tsdf_hash_sdf_linearize": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I],
     "tsdf_dense_sample": [_P, _P, _I64, _P, _P, _P, _I],
     "tsdf_hash_sample": [_P, _P, _I64, _P, _P, _P, _I],
+    "tsdf_dense_merge": [_P, _P, _P, _P, _P, _I],
+    "tsdf_hash_merge": [_P, _P, _P, _P, _P, _I],
+    "tsdf_merge_last_profile": [_P, _P],
 }
 
 _lib = None

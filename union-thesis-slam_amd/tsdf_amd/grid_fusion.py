@@ -122,6 +122,30 @@ def raycast_call(fn, handle, device, vol_bnds, voxel_size, cam_intr, cam_pose, h
     return d, n, c
 
 
+def merge_call(fn, handle, other, src_to_dst, return_info):
+    """The merge entry points' host side (tsdf_dense_merge / tsdf_hash_merge): `other` is a TSDFVolume
+    or a HashTable."""
+    from . import hash_fusion
+    if isinstance(other, TSDFVolume):
+        src = (other._h, None)
+    elif isinstance(other, hash_fusion.HashTable):
+        src = (None, other._h)
+    else:
+        raise TypeError("merge takes a TSDFVolume or a HashTable")
+    info = _ffi.MergeInfo()
+    _ffi.call(fn, handle, src[0], src[1], _ffi.ptr(_ffi.f64(src_to_dst, 16)), ctypes.byref(info), 0)
+    return info.as_dict() if return_info else info.samples
+
+
+def merge_last_profile():
+    """(ms, candidate_bricks) of the calling thread's last merge (tsdf_merge_last_profile): the HIP-event
+    time of its launches when the destination had profiling on (else -1), and the destination
+    bricks the cull let through."""
+    ms, cand = ctypes.c_double(-1.0), ctypes.c_int64(-1)
+    _ffi.call("tsdf_merge_last_profile", ctypes.byref(ms), ctypes.byref(cand))
+    return ms.value, cand.value
+
+
 class TSDFVolume:
     """Volumetric TSDF Fusion of RGB-D Images, on an MI355X.
 
@@ -366,6 +390,18 @@ class TSDFVolume:
         2 and 3.  Arrays for an array, CUDA tensors for a contiguous float64 CUDA tensor."""
         from . import tracking
         return tracking.sample_call("tsdf_dense_sample", self._h, self.device, points)
+
+    def merge(self, other, src_to_dst=np.eye(4), return_info=False):
+        """Merge another fused map -- a TSDFVolume or a HashTable on the same device -- into this one
+        (tsdf_dense_merge).  src_to_dst (4,4) is rigid and takes the other map's world
+        coordinates to this one's.  Every voxel of this volume whose trilinear cell in `other` is
+        observed takes the sampled tsdf, the least corner weight and the nearest corner's colour by the
+        integrate's weighted update; the rest keep their bytes.  With the identity (or a shift by whole
+        voxels) between equal lattices the observed voxels are copied bit for bit: submaps are joined,
+        a volume is re-centred, a coarse map is resampled into a finer one (not the reverse: the
+        other's truncation must not be below this one's).  Returns the number of voxels updated; with
+        return_info the dict samples, bricks_updated, blocks_allocated."""
+        return merge_call("tsdf_dense_merge", self._h, other, src_to_dst, return_info)
 
     def get_point_cloud(self):
         """grid_fusion.py:322-338: (N, 6) float32 rows x, y, z, r, g, b of the mesh vertices."""

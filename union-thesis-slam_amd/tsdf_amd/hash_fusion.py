@@ -322,6 +322,12 @@ class HashTable:
         from . import tracking
         return tracking.sample_call("tsdf_hash_sample", self._h, self.device, points)
 
+    def merge(self, other, src_to_dst=np.eye(4), return_info=False):
+        """TSDFVolume.merge into this table (tsdf_hash_merge): every sampled voxel receives
+        an entry, and exactly the blocks with a sample are allocated (the table and the pool grow as
+        needed)."""
+        return grid_fusion.merge_call("tsdf_hash_merge", self._h, other, src_to_dst, return_info)
+
     def extract_mesh(self, normals=True, colors=True, faces=True, keys=False):
         """Marching cubes at level 0 over the table's live blocks (tsdf_hash_extract_mesh): the
         mesh of get_state()'s volume, byte for byte what _as_grid().extract_mesh() gives, without
