@@ -47,11 +47,13 @@ def _lerp(a, b, t):
 
 
 def linearize_color(depth, rgb, Kf, M, model_depth, model_colors, Km, *, dist_max=0.1, color_max_diff=40.0, stride=1,
-                    invalid_65535=False, **_):
+                    invalid_65535=False, swap_gradient_focals=False, **_):
     """The colour half of one linearisation.  Returns a dict like icp_ref.linearize's: code (Hf,Wf)
     u8 (0 .. 5), resid (Hf,Wf) f32 (intensity levels; 0 where the code is not 5), sums / abs_sums
     (28,), inliers, candidates (codes 2 .. 5), and J (N,6) f32 / r (N,) f32 / p (N,3) f32 /
-    g (N,3) f32 / If (N,) f32 (the frame's intensity) of the inliers in row-major pixel order."""
+    g (N,3) f32 / If (N,) f32 (the frame's intensity) of the inliers in row-major pixel order.
+    swap_gradient_focals is a deliberate fault for tests/test_cameras_cpu.py: the Jacobian line alone
+    scales Gx by fym and Gy by fxm; the codes and residuals stay what they are."""
     d = I.depth_metres(depth, invalid_65535)
     Hf, Wf = d.shape
     If = intensity(rgb)
@@ -95,7 +97,8 @@ def linearize_color(depth, rgb, Kf, M, model_depth, model_colors, Km, *, dist_ma
         code[alive & ~ok] = 4
         alive &= ok
         code[alive] = 5
-        a, b, iz = Gx * fxm, Gy * fym, F32(1) / p[2]
+        sx, sy = (fym, fxm) if swap_gradient_focals else (fxm, fym)
+        a, b, iz = Gx * sx, Gy * sy, F32(1) / p[2]
         gx, gy = a * iz, b * iz
         g = (gx, gy, -((gx * p[0] + gy * p[1]) * iz))
         pxg = I._cross(p, g)
