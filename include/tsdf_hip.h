@@ -514,7 +514,19 @@ int tsdf_hash_frames_per_launch(tsdf_hash_t* h, int* n);
  * bounds[2r] = min(bounds[2r], min over points), bounds[2r+1] = max(...) for r = x, y, z
  * (bounds is in/out: the demo starts from zeros).  Optional outputs: max_depth (n_frames
  * doubles, metres) and frustum_pts (n_frames x 3 x 5 doubles, get_view_frustum's array).
- * All values equal the reference's f64 results bit for bit. */
+ * Where a frame's max depth is finite and every coordinate it gives is, all values equal the
+ * reference's f64 results bit for bit.  F64_M frames from float-depth sources hold more than that,
+ * and for them the contract is this (it departs from np.max in the first point only):
+ *   - a NaN pixel is ignored: the max depth is the maximum over the other pixels (np.max would
+ *     return the NaN); negative and infinite pixels take part like any value;
+ *   - a frame without a single non-NaN pixel has max depth 0.0, like a u16 frame whose pixels are
+ *     all invalid: its five points are the camera centre;
+ *   - a max depth of +inf, or one whose product with a pixel offset overflows, gives infinite
+ *     coordinates, and NaN ones where the infinity meets a zero or its opposite (0 * inf, inf - inf).
+ *     frustum_pts reports both as computed; bounds folds the infinite ones and passes over the NaN
+ *     ones (fmin / fmax), so it never comes back holding a NaN;
+ *   - frames that are -inf throughout are not specified.
+ * tests/test_hostile_depth_gpu.py; oracle.frame_max_depth / frustum_bounds state the same rule. */
 int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int height, int width,
                         const double K[9], const double* cam_poses, int flags, int device,
                         double* max_depth, double* frustum_pts, double bounds[6]);

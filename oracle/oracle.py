@@ -316,12 +316,21 @@ def view_frustum(max_depth: float, H: int, W: int, K, pose) -> np.ndarray:
     return out
 
 
+def frame_max_depth(depth_im) -> float:
+    """The max depth tsdf_frustum_bounds takes from a frame (include/tsdf_hip.h): np.max over the
+    pixels that are not NaN (the reference's np.max would return the NaN), 0.0 when there is none."""
+    m = np.fmax.reduce(np.asarray(depth_im, dtype=np.float64), axis=None)
+    return 0.0 if np.isnan(m) else float(m)
+
+
 def frustum_bounds(max_depths, H, W, K, poses, init=None) -> np.ndarray:
     """grid_demo1.py:50-64: running min/max of the frustum points, starting from `init`
-    (the demo starts from zeros).  Returns (3, 2)."""
+    (the demo starts from zeros).  Returns (3, 2).  A NaN coordinate (0 * inf under an infinite max
+    depth) is not folded, an infinite one is: tsdf_frustum_bounds' contract.  For finite max depths
+    this is the demo's np.minimum / np.maximum to the bit."""
     b = np.zeros((3, 2)) if init is None else np.array(init, dtype=np.float64)
     for d, p in zip(max_depths, poses):
         v = view_frustum(d, H, W, K, p)
-        b[:, 0] = np.minimum(b[:, 0], v.min(axis=1))
-        b[:, 1] = np.maximum(b[:, 1], v.max(axis=1))
+        b[:, 0] = np.fmin(b[:, 0], np.fmin.reduce(v, axis=1))
+        b[:, 1] = np.fmax(b[:, 1], np.fmax.reduce(v, axis=1))
     return b

@@ -19,6 +19,9 @@ Fixtures written (data only -- inputs and expected outputs, no reference source)
   golden/hash_c1_remove.npz    lounge f0, remove_hash_entry over a rule's set, lounge f1: the returns,
                                entry counts, the removed voxels that are back, a state digest (G2r)
   golden/synth_c1.npz          two synthetic frames (tsdf_amd.scene) -> 128^3 @ 8 cm room (G2s)
+  golden/hostile_depth.npz     tests/hostile_depth.py's NaN / infinite / negative / tiny / far / huge f64
+                               depth frames -> 48x40x24 @ 2 cm, grid CPU path and HashTable.integrate,
+                               at 128x96 and 126x95 (G2x)
   golden/lounge2cm_kat.json    lounge 2 cm, frames 0-9: per-frame counts + final-state digest (G3)
   golden/lounge512_kat.json    lounge f0 -> 512^3 @ 2 cm: count + digest (G5)
   golden/frustum_bounds.npz    lounge frames 0-999: per-frame max depth (mm, after the demo's
@@ -267,6 +270,10 @@ def inner():
             print("synth frame", f, "updated", int(res["f%d_nupd" % f]))
         np.savez_compressed(os.path.join(GOLD, "synth_c1.npz"), **res)
 
+    # ---- G2x hostile f64 depth (tests/hostile_depth.py) -------------------------------------
+    if want("hostile"):
+        gen_hostile(grid_fusion, hash_fusion)
+
     # ---- G3 lounge 2 cm, 10 frames -----------------------------------------------------
     if want("lounge2cm"):
         vol = grid_fusion.TSDFVolume(np.array(LOUNGE_BNDS), 0.02, use_gpu=False)
@@ -305,6 +312,77 @@ def inner():
         print("lounge512", kat)
         with open(os.path.join(GOLD, "lounge512_kat.json"), "w") as fh:
             json.dump(kat, fh, indent=1)
+
+
+def gen_hostile(grid_fusion, hash_fusion):
+    """G2x: the frames of tests/hostile_depth.py (NaN, infinities, negatives, tiny, far and huge f64
+    depths) through the reference's CPU TSDFVolume.integrate and its HashTable.integrate, once per
+    image size.  Stored per size s: the inputs (depth, the three colour images and which frame uses
+    which, poses, weights, K, bounds), per frame the voxels whose weight the frame changed with
+    their new tsdf / weight / colour (a packed mask over the C-order voxels, then the values of its set
+    bits in order; applied frame after frame they give the sparse state after every
+    frame) and the update count, and the hash path's final entries (mask and values alike) with its per-frame entry counts."""
+    import time
+    import warnings
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import hostile_depth as H
+    res = {"K": H.K, "bounds": np.array(H.BOUNDS), "voxel_size": np.float64(H.VS), "class_names": np.array(list(H.CLASSES)),
+           "class_values": H.VALUES}
+    for s in H.SIZES:
+        names, depth, rgb, poses, ow = H.sequence(s)
+        uniq = np.stack([H.rgb(s, k) for k in range(3)])
+        index = np.arange(len(names)) % 3
+        assert np.array_equal(uniq[index], rgb)
+        res.update({s + "_names": np.array(names), s + "_depth": depth, s + "_rgb": uniq, s + "_rgb_index": index.astype(np.uint8),
+                    s + "_poses": poses, s + "_obs_weight": ow})
+        vol = grid_fusion.TSDFVolume(np.array(H.BOUNDS), H.VS, use_gpu=False)
+        assert tuple(int(d) for d in vol._vol_dim) == H.DIMS and vol._tsdf_vol_cpu.size < 65536
+        ht = hash_fusion.HashTable(np.array(H.BOUNDS), H.VS, 100000, 0.75, False)
+        prev = np.zeros(vol._weight_vol_cpu.shape, np.float32)
+        t_hash, entries = 0.0, []
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # (overflow in 1.7e308 / trunc; invalid in inf - inf never occurs)
+            for f in range(len(names)):
+                vol.integrate(rgb[f], depth[f], H.K, poses[f], obs_weight=float(ow[f]))
+                w = vol._weight_vol_cpu
+                prev_flat = prev.reshape(-1)
+                idx = np.flatnonzero(w.reshape(-1) != prev_flat)
+                p = "%s_f%d_" % (s, f)
+                res[p + "mask"] = np.packbits(w.reshape(-1) != prev_flat)
+                res[p + "tsdf"] = vol._tsdf_vol_cpu.reshape(-1)[idx].copy()
+                res[p + "weight"] = w.reshape(-1)[idx].copy()
+                res[p + "color"] = vol._color_vol_cpu.reshape(-1)[idx].copy()
+                res[p + "nupd"] = np.int64(len(idx))
+                prev = w.copy()
+                t0 = time.time()
+                ht.integrate(rgb[f], depth[f], H.K, poses[f], obs_weight=float(ow[f]))
+                t_hash += time.time() - t0
+                entries.append(ht.count_num_hash_entries())
+        assert not np.isnan(vol._tsdf_vol_cpu).any()
+        pos, sdf, w, col = [], [], [], []
+        for b in ht._hash_table:
+            if b is None:
+                continue
+            for j in range(5):
+                e = b.get_ith_entry(j)
+                if e is not None and e.get_voxel() is not None:
+                    pos.append([int(q) for q in e.get_position()])
+                    sdf.append(float(e.get_voxel().get_sdf()))
+                    w.append(float(e.get_voxel()._weight))
+                    col.append(float(e.get_voxel().get_color()))
+        pos = np.array(pos, np.int64)
+        order = np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))
+        has = np.zeros(H.DIMS, bool)
+        has[tuple(pos.T)] = True  # (C-order of the set bits == the lexsort order)
+        res.update({s + "_hash_mask": np.packbits(has.reshape(-1)), s + "_hash_sdf": np.array(sdf)[order],
+                    s + "_hash_weight": np.array(w)[order].astype(np.float32), s + "_hash_color": np.array(col)[order].astype(np.float32),
+                    s + "_hash_entries": np.array(entries, np.int64)})
+        assert np.array_equal(res[s + "_hash_weight"].astype(np.float64), np.array(w)[order])
+        assert np.array_equal(res[s + "_hash_color"].astype(np.float64), np.array(col)[order])
+        print("hostile", s, "updates", [int(res["%s_f%d_nupd" % (s, f)]) for f in range(len(names))], "entries", entries[-1],
+              "hash path %.1f s" % t_hash)
+    np.savez_compressed(os.path.join(GOLD, "hostile_depth.npz"), **res)
+    print("hostile_depth.npz", os.path.getsize(os.path.join(GOLD, "hostile_depth.npz")), "bytes")
 
 
 def gen_frustum(grid_fusion, cam_intr):

@@ -740,7 +740,11 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
     }
 }
 
-// np.minimum(1, (depth - z) / trunc) (grid_fusion.py:284-286; the quotient is never NaN)
+// np.minimum(1, (depth - z) / trunc) (grid_fusion.py:284-286).  diff is never NaN (a NaN depth fails
+// dep > 0), but div_rn's quotient is one where diff is +inf or diff / trunc overflows (depth +inf,
+// 1.7e308): its correction step is fma(-inf, trunc, inf).  The result is still the reference's 1
+// because fmin returns its other operand for a NaN -- a select such as q > 1 ? 1 : q would store
+// the NaN.  tests/test_hostile_depth_gpu.py holds this against the oracle.
 __device__ inline double dist_of(double trunc, double rtrunc, double diff) {
     return fmin(div_rn(diff, trunc, rtrunc), 1.0);
 }
@@ -1694,6 +1698,13 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(TSDF_HASH_W
     flush_stats(s_stat, stats);
 }
 
+// An f64 depth narrowed for the max-depth pyramid.  The cull reads a texel of 0 as "no depth under
+// it" (cull_brick: dmax > 0), so the narrowing must not take a positive depth there: one below 2^-150
+// rounds to 0.0f, and a tile holding nothing larger lost the voxels with 0 < z <= trunc that the
+// reference updates.  Raised to FLT_MIN the texel stays an upper bound, which is all the cull needs
+// (depths beyond FLT_MAX become +inf, an upper bound too).  NaN, negatives and -0.0 give 0.
+__device__ inline float pyr_depth(double d) { return d > 0.0 ? fmaxf((float)d, 1.17549435e-38f) : 0.0f; }
+
 // Per frame, before the cull (one pass over the image): the packed RGB8 image, the max-depth
 // pyramid levels 1..6
 // (texel = max over a 2^L x 2^L block, metres, 0 for invalid/outside) and the reset of the
@@ -1737,8 +1748,8 @@ __device__ inline void prep_vec_tile(const Batch& bt, unsigned int* count, int t
             if (DK == 1) {  // f64 metres (the reference's own depth_im)
                 const double2 d0 = *(const double2*)((const double*)fr.depth_src + p);
                 const double2 d1 = *(const double2*)((const double*)fr.depth_src + p + 2);
-                ma = fmaxf(ma, fmaxf((float)d0.x, (float)d0.y));
-                mb = fmaxf(mb, fmaxf((float)d1.x, (float)d1.y));
+                ma = fmaxf(ma, fmaxf(pyr_depth(d0.x), pyr_depth(d0.y)));
+                mb = fmaxf(mb, fmaxf(pyr_depth(d1.x), pyr_depth(d1.y)));
             } else {
                 dd = *(const uint2*)((const unsigned short*)fr.depth_src + p);
                 if (fr.depth_mask) {  // the demos' depth_im[depth_im == 65.535] = 0
@@ -1843,7 +1854,7 @@ __global__ __launch_bounds__(1024) void k_prep(Batch bt, unsigned int* count) {
                     }
                     d = (float)v * 1e-3f;
                 } else {
-                    d = (float)((const double*)fr.depth_src)[p];
+                    d = pyr_depth(((const double*)fr.depth_src)[p]);
                 }
                 if (CK == 0 && rgbx) {
                     const unsigned char* q = (const unsigned char*)fr.color + 3 * (size_t)p;

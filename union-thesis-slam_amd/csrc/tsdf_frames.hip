@@ -7,7 +7,8 @@
 // HBM-streaming reduction: 2 B/px for u16, 8 B/px for f64), k_frustum turns each maximum and
 // pose into the 5 frustum points -- with the reference's f64 operation order and the OpenBLAS
 // dgemm FMA chain of rigid_transform -- and folds them into 6 order-preserving keys with
-// atomicMin/atomicMax.  Maxima and bounds are exact: identical to the reference's f64 values.
+// atomicMin/atomicMax.  Maxima and bounds are exact: identical to the reference's f64 values
+// wherever those are finite; NaN pixels and infinite maxima follow include/tsdf_hip.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -31,16 +32,22 @@ __device__ __host__ inline double dval(unsigned long long k) {
     return x;
 }
 
+// A frame's max depth from its key.  Key 0 lies below the key of every value that is not a NaN (it
+// decodes to a NaN itself): it is what the keys start from, and what a frame without a single
+// non-NaN pixel leaves.  Such a frame has max depth 0.0, like a u16 frame whose pixels are all invalid.
+__device__ __host__ inline double frame_max_of(unsigned long long k) { return k ? dval(k) : 0.0; }
+
 constexpr int kMaxWG = 256;
 
 // Max depth of frame blockIdx.y (metres as the reference sees it: f64(mm) / 1000, or the f64
 // value), as a key in keys[frame].  invalid_65535: the 7-Scenes convention of the demos
-// (grid_demo1.py:82: 65.535 m -> 0).
+// (grid_demo1.py:82: 65.535 m -> 0).  f64: the maximum over the pixels that are not NaN; np.max
+// would return the NaN, and one "no return" pixel would cost the frame its frustum.
 template <int DK>
 __global__ __launch_bounds__(kMaxWG) void k_frame_max(const void* depth, long long npx, int invalid_65535,
                                                       unsigned long long* keys) {
     const long long f = blockIdx.y;
-    unsigned long long best = dkey(DK == 0 ? 0.0 : -1.0 / 0.0);
+    unsigned long long best = 0ull;  // (frame_max_of: no pixel yet)
     if (DK == 0) {
         const unsigned short* d = (const unsigned short*)depth + f * npx;
         unsigned m = 0;
@@ -55,7 +62,7 @@ __global__ __launch_bounds__(kMaxWG) void k_frame_max(const void* depth, long lo
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npx;
              i += (long long)gridDim.x * blockDim.x) {
             const double v = d[i];
-            if (v == v) best = max(best, dkey(v));  // np.max would propagate a NaN; skip it
+            if (v == v) best = max(best, dkey(v));
         }
     }
     for (int o = 32; o > 0; o >>= 1) best = max(best, (unsigned long long)__shfl_xor(best, o));
@@ -75,7 +82,7 @@ __global__ void k_frustum(int n, int H, int W, const double* __restrict__ K,
                           double* __restrict__ pts, unsigned long long* bkeys) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
-    const double dmax = dval(maxk[f]);
+    const double dmax = frame_max_of(maxk[f]);
     const double* T = poses + 16 * (long long)f;
     const double us[5] = {0.0, 0.0, 0.0, (double)W, (double)W};
     const double vs[5] = {0.0, 0.0, (double)H, 0.0, (double)H};
@@ -88,6 +95,9 @@ __global__ void k_frustum(int n, int H, int W, const double* __restrict__ K,
             const double* t = T + 4 * r;
             const double c = fma(t[3], 1.0, fma(t[2], z, fma(t[1], y, t[0] * x)));
             if (pts) pts[15 * (long long)f + 5 * r + j] = c;
+            // an infinite dmax gives infinite coordinates, and NaN ones where it meets a zero
+            // (0 * inf, inf - inf): the points report both, the bounds fold the infinities and
+            // pass over the NaNs (fmin / fmax return the other operand; point 0 is always finite)
             lo[r] = fmin(lo[r], c);
             hi[r] = fmax(hi[r], c);
         }
@@ -179,7 +189,7 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     if (frustum_pts) TSDF_HIP(hipMemcpyAsync(frustum_pts, dpts, sizeof(double) * 15 * n_frames, hipMemcpyDeviceToHost, s));
     TSDF_HIP(hipStreamSynchronize(s));
     if (max_depth)
-        for (int f = 0; f < n_frames; ++f) max_depth[f] = dval(hk[f]);
+        for (int f = 0; f < n_frames; ++f) max_depth[f] = frame_max_of(hk[f]);
     // the demo's np.minimum / np.maximum with the incoming bounds (it starts from zeros)
     for (int r = 0; r < 3; ++r) {
         bounds[2 * r] = std::fmin(bounds[2 * r], dval(hb[r]));
