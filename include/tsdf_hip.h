@@ -293,7 +293,12 @@ int tsdf_dense_raycast(tsdf_dense_t* h, int height, int width, const double K[9]
  * same state and inputs give byte-identical results (no floating-point atomics).  TSDF_E_ARG:
  * stride < 1, max_iter outside [1, TSDF_ICP_MAX_ITER], dist_max <= 0, cos_min outside [-1, 1],
  * a negative min_inliers / eps, a bad image size or depth_kind, a NULL depth / K / pose_guess /
- * params / out_pose, and whatever the raycast refuses (its z arguments, a cyclic column shard). */
+ * params / out_pose, a pose_guess whose rotation block is not orthonormal with determinant +1
+ * within 1e-3 (a scaled, sheared, mirrored, zero or NaN rotation: such a guess makes systems of
+ * condition 1e15 and steps of kilometres; a pose read from text with eight digits passes; the
+ * translation is not looked at, a NaN or infinite one ends lost), and whatever the raycast refuses
+ * (its z arguments, a cyclic column shard).  A refused call writes to none of its outputs.  The
+ * _rgbd, _sdf and hash entry points refuse the same. */
 int tsdf_dense_track(tsdf_dense_t* h, const void* depth, int depth_kind, int height, int width,
                      const double K[9], const double pose_guess[16], const tsdf_icp_params_t* params,
                      double z_near, double z_far, double z_step, double out_pose[16],
@@ -524,9 +529,16 @@ int tsdf_hash_frames_per_launch(tsdf_hash_t* h, int* n);
  *   - a max depth of +inf, or one whose product with a pixel offset overflows, gives infinite
  *     coordinates, and NaN ones where the infinity meets a zero or its opposite (0 * inf, inf - inf).
  *     frustum_pts reports both as computed; bounds folds the infinite ones and passes over the NaN
- *     ones (fmin / fmax), so it never comes back holding a NaN;
+ *     ones (fmin / fmax), so a depth image never makes it come back holding a NaN;
+ *   - a NaN coordinate that the pose or K made -- one that a max depth of 1 m gives as well: a NaN
+ *     in cam_pose, fx == 0, an infinite principal point -- is the caller's lost tracking and stays
+ *     visible as in the reference, whose np.minimum / np.amin keep it: both bounds of that axis come
+ *     back NaN, and NaN bounds passed in stay NaN.  The 1 m probe is the whole rule: a finite pose
+ *     whose products overflow to inf - inf only at the frame's real max depth counts as depth-made
+ *     and is passed over, where the reference would keep that NaN too;
  *   - frames that are -inf throughout are not specified.
- * tests/test_hostile_depth_gpu.py; oracle.frame_max_depth / frustum_bounds state the same rule. */
+ * tests/test_hostile_depth_gpu.py, tests/test_hostile_pose_gpu.py; oracle.frame_max_depth / frustum_bounds
+ * state the same rule. */
 int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int height, int width,
                         const double K[9], const double* cam_poses, int flags, int device,
                         double* max_depth, double* frustum_pts, double bounds[6]);

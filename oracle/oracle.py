@@ -110,12 +110,13 @@ class OracleTSDFVolume:
         self._color_vol_cpu = np.zeros(shape, np.float32)
         self.last_updated = None
 
-    def integrate(self, color_im, depth_im, cam_intr, cam_pose, obs_weight=1.0, want_mask=False):
+    def integrate(self, color_im, depth_im, cam_intr, cam_pose, obs_weight=1.0, want_mask=False, rows=None):
+        """`rows`: inv(cam_pose) itself, for matrices no cam_pose inverts to (cam_pose is then unused)."""
         im_h, im_w = depth_im.shape
         col = fold_color(color_im)
         depth = np.ascontiguousarray(depth_im, dtype=np.float64)
         K = np.ascontiguousarray(cam_intr, dtype=np.float64).reshape(9)
-        Tinv = np.ascontiguousarray(np.linalg.inv(cam_pose), dtype=np.float64).reshape(16)
+        Tinv = np.ascontiguousarray(np.linalg.inv(cam_pose) if rows is None else rows, dtype=np.float64).reshape(16)
         upd = np.zeros(self._tsdf_vol_cpu.size, np.uint8) if want_mask else None
         n = lib().oracle_dense_integrate_rows(
             _p(self._local_dim), _p(self._off), _p(self._xmap), _p(self._vol_origin), self._voxel_size, self._trunc_margin,
@@ -142,12 +143,12 @@ class OracleHashVolume:
         self.color = np.zeros(shape, np.float64)
         self.new_keys = None
 
-    def integrate(self, color_im, depth_im, cam_intr, cam_pose, obs_weight=1.0):
+    def integrate(self, color_im, depth_im, cam_intr, cam_pose, obs_weight=1.0, rows=None):
         im_h, im_w = depth_im.shape
         col = fold_color(color_im)
         depth = np.ascontiguousarray(depth_im, dtype=np.float64)
         K = np.ascontiguousarray(cam_intr, dtype=np.float64).reshape(9)
-        Tinv = np.ascontiguousarray(np.linalg.inv(cam_pose), dtype=np.float64).reshape(16)
+        Tinv = np.ascontiguousarray(np.linalg.inv(cam_pose) if rows is None else rows, dtype=np.float64).reshape(16)
         nk = np.zeros(self.sdf.size, np.uint8)
         n = lib().oracle_hash_integrate(
             _p(self._vol_dim), _p(self._vol_origin), self._voxel_size, self._trunc_margin,
@@ -327,10 +328,15 @@ def frustum_bounds(max_depths, H, W, K, poses, init=None) -> np.ndarray:
     """grid_demo1.py:50-64: running min/max of the frustum points, starting from `init`
     (the demo starts from zeros).  Returns (3, 2).  A NaN coordinate (0 * inf under an infinite max
     depth) is not folded, an infinite one is: tsdf_frustum_bounds' contract.  For finite max depths
-    this is the demo's np.minimum / np.maximum to the bit."""
+    this is the demo's np.minimum / np.maximum to the bit, the NaN they keep for a NaN pose, fx == 0 or
+    NaN bounds passed in included."""
     b = np.zeros((3, 2)) if init is None else np.array(init, dtype=np.float64)
+    stay = np.isnan(b)
     for d, p in zip(max_depths, poses):
         v = view_frustum(d, H, W, K, p)
         b[:, 0] = np.fmin(b[:, 0], np.fmin.reduce(v, axis=1))
         b[:, 1] = np.fmax(b[:, 1], np.fmax.reduce(v, axis=1))
+        # a NaN that a depth of 1 m gives as well is the pose's or K's: it stays, as in np.minimum / np.amin
+        stay |= (np.isnan(v) & np.isnan(view_frustum(1.0, H, W, K, p))).any(axis=1)[:, None]
+    b[stay] = np.nan
     return b

@@ -82,6 +82,7 @@ def linearize_color(depth, rgb, Kf, M, model_depth, model_colors, Km, *, dist_ma
         xi = np.where(alive, x0, 1).astype(np.int64)
         yi = np.where(alive, y0, 1).astype(np.int64)
         xi, yi = np.clip(xi, 0, max(Wm - 2, 0)), np.clip(yi, 0, max(Hm - 2, 0))  # (dead pixels only)
+        assert ((yi >= 0) & (yi + 1 < T.shape[0]) & (xi >= 0) & (xi + 1 < T.shape[1])).all()
         t00, t01, t10, t11 = T[yi, xi], T[yi, xi + 1], T[yi + 1, xi], T[yi + 1, xi + 1]
         ok = (t00[..., 3] > 0) & (t01[..., 3] > 0) & (t10[..., 3] > 0) & (t11[..., 3] > 0)
         code[alive & ~ok] = 2

@@ -94,6 +94,7 @@ def linearize(depth, Kf, M, model_depth, model_normals, Km, model_pose, *, dist_
         alive &= ok
         um = np.where(alive, uf, 0).astype(np.int64)
         vm = np.where(alive, vf, 0).astype(np.int64)
+        assert ((vm >= 0) & (vm < Hm) & (um >= 0) & (um < Wm)).all()  # (every gather index in range, whatever M and K)
         dm = Dm[vm, um]
         nw = [Nm[vm, um, k] for k in range(3)]
         ok = (dm > 0) & ~((nw[0] == 0) & (nw[1] == 0) & (nw[2] == 0))

@@ -95,6 +95,7 @@ def sample(dst, src, s_t, s_w, s_c, T):
     for s in range(8):
         dx, dy, dz = s >> 2, (s >> 1) & 1, s & 1
         idx = (l[0] + dx * nn[0], l[1] + dy * nn[1], l[2] + dz * nn[2])
+        assert all(((i >= 0) & (i < d)).all() for i, d in zip(idx, s_t.shape))  # (every gather index in range)
         c.append(s_t[idx])
         w.append(s_w[idx])
     seen = np.ones(len(l[0]), bool)

@@ -12,6 +12,24 @@ def _lerp(a, b, t):
     return a + t * (b - a)
 
 
+def clamp_index(q):
+    """q with the kernels' clamp before every float -> int conversion (floor_i, tsdf_cell.h):
+    fminf(fmaxf(q, -1e9), 1e9), whose fmaxf drops a NaN -- so NaN becomes -1e9, far outside every
+    volume -- and whose result always converts to an integer exactly."""
+    with np.errstate(invalid="ignore"):
+        c = np.where(np.isnan(q), -1.0e9, np.clip(q, -1.0e9, 1.0e9))
+    assert np.isfinite(c).all() and (np.abs(c) <= 1.0e9).all()
+    return c
+
+
+def assert_in_range(index, shape):
+    """Every gather of the restatements goes through here: an index outside the array is what the
+    kernel must not form either."""
+    for i, n in zip(index, shape):
+        assert ((i >= 0) & (i < n)).all(), (int(np.min(i)), int(np.max(i)), int(n))
+    return index
+
+
 def _cell(tsdf, weight, l, dims, dtype):
     """Corner values c[s] (s = dx*4 + dy*2 + dz) of the cells at local indices l (N, 3), and the
     cells' validity: 8 corners inside the volume, all with weight > 0."""
@@ -19,7 +37,7 @@ def _cell(tsdf, weight, l, dims, dtype):
     lc = np.clip(l, 0, np.maximum(dims - 2, 0))
     c, valid = [], inside.copy()
     for s in range(8):
-        i = (lc[:, 0] + (s >> 2), lc[:, 1] + ((s >> 1) & 1), lc[:, 2] + (s & 1))
+        i = assert_in_range((lc[:, 0] + (s >> 2), lc[:, 1] + ((s >> 1) & 1), lc[:, 2] + (s & 1)), tsdf.shape)
         c.append(tsdf[i].astype(dtype))
         valid &= weight[i] > 0
     return c, valid
@@ -75,7 +93,7 @@ def raycast(tsdf, weight, color, origin, voxel_size, cam_intr, cam_pose, hw, z_n
 
     def sample(idx, z):
         q = qo[idx] + qd[idx] * z[:, None] if np.ndim(z) else qo[idx] + qd[idx] * z
-        i0 = np.floor(np.clip(q, -1.0e9, 1.0e9)).astype(np.int64)
+        i0 = np.floor(clamp_index(q)).astype(np.int64)
         t = q - i0.astype(dtype)
         return q, i0 - off, t
 
@@ -114,9 +132,9 @@ def raycast(tsdf, weight, color, origin, voxel_size, cam_intr, cam_pose, hw, z_n
                 zstar = z0 + zs * (f0 / (f0 - f1))
                 depth[hi] = zstar
                 q, ls, ts = sample(hi, zstar)
-                rv = np.rint(np.clip(q, -1.0e9, 1.0e9)).astype(np.int64) - off
+                rv = np.rint(clamp_index(q)).astype(np.int64) - off
                 rv = np.clip(rv, 0, dims - 1)
-                colors[hi] = decode_color(color[rv[:, 0], rv[:, 1], rv[:, 2]])
+                colors[hi] = decode_color(color[assert_in_range((rv[:, 0], rv[:, 1], rv[:, 2]), color.shape)])
                 cs, vs_ = _cell(tsdf, weight, ls, dims, dtype)
                 gx, gy, gz = _gradient(cs, ts)
                 ln = np.sqrt((gx * gx + gy * gy) + gz * gz)

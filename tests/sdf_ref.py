@@ -23,14 +23,14 @@ def cell(tsdf, weight, q, index_offset=(0, 0, 0)):
     g 3 x (N,) f32, i0 (N, 3) global cell indices); f and g are meaningful for codes 4 and 6."""
     q = np.asarray(q, dtype=F32)
     dims = np.array(tsdf.shape, dtype=np.int64)
-    i0 = np.floor(np.clip(q, F32(-1.0e9), F32(1.0e9))).astype(np.int64)
+    i0 = np.floor(R.clamp_index(q)).astype(np.int64)
     t = q - i0.astype(F32)
     l = i0 - np.asarray(index_offset, dtype=np.int64)
     inside = np.all((l >= 0) & (l <= dims - 2), axis=1)
     lc = np.clip(l, 0, np.maximum(dims - 2, 0))
     c, seen, flat = [], np.ones(len(q), bool), np.zeros(len(q), bool)
     for s in range(8):
-        i = (lc[:, 0] + (s >> 2), lc[:, 1] + ((s >> 1) & 1), lc[:, 2] + (s & 1))
+        i = R.assert_in_range((lc[:, 0] + (s >> 2), lc[:, 1] + ((s >> 1) & 1), lc[:, 2] + (s & 1)), tsdf.shape)
         c.append(tsdf[i].astype(F32))
         seen &= weight[i] > 0
         flat |= np.abs(c[-1]) >= 1

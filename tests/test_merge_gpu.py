@@ -318,9 +318,24 @@ def test_refusals(gf, hf, sources, dk):
     bad[2][3, 0] = 1e-3            # last row
     bad[3][0, 3] = np.inf
     bad[4][1, 1] = np.nan
+    for r in range(3):             # NaN, +inf and -inf in each of the 12 entries
+        for c in range(4):
+            for v in (np.nan, np.inf, -np.inf):
+                bad.append(np.array(T))
+                bad[-1][r, c] = v
+    import hostile_pose
+    bad += list(hostile_pose.merge_nonrigid(T).values())  # scales, a shear, a mirror: no rigid motion (include/tsdf_hip.h)
     for b in bad:
         assert not M.check_transform(b)
         refused(h._h, sd, None, _ffi.ptr(_ffi.f64(b, 16)), None, 0)
+        same_state(h.get_state(), before, dk)
+    # a rigid transform 1e30 m away is accepted and, as in merge_ref, finds every voxel outside the source
+    far = hostile_pose.merge_far(T)
+    assert M.check_transform(far) and (M.sample(dst, M.SRC, *M.source_state(), far)[0] == M.OUTSIDE).all()
+    for src in sources.values():
+        info_far = h.merge(src, far, return_info=True)
+        assert info_far["samples"] == 0 and info_far["bricks_updated"] == 0, info_far
+        same_state(h.get_state(), before, dk)
     cyc = gf.TSDFVolume(M.SRC.bounds(), M.SRC.vs, shard=(0, 2))
     refused(h._h, cyc._h, None, Tp, None, 0)                      # a cyclic column shard as the source
     hs = hf.HashTable(M.SRC.bounds(), M.SRC.vs, 1 << 10, shard=0, n_shards=2)

@@ -14,7 +14,14 @@
  *   (d) a non-finite row, intrinsic or an oversized image gives zmin_hi = INT_MAX;
  *   (e) the texel's invalid-depth sentinel fails the truncation test for the smallest positive z
  *       and the largest trunc of the texel route, and valid u16 depths convert as before.
- * Prints "pixel_fixed <case> checked N fine F bad B" per case (expected B = 0).
+ *   (hostile) hostile rows and intrinsics (tests/hostile_pose.py): NaN, infinities and a translation whose
+ *       T * f overflows give zmin_hi = INT_MAX and, where an entry is non-finite, frame_is_dead; the
+ *       finite ones -- negative, zero, tiny and huge focal lengths, scaled, sheared and mirrored rows,
+ *       translations of 1e30, 1e39 and 1e300, a zero third row, the zero matrix -- either take no fast
+ *       path or return a zmin above which, with the numerator bound taken here from |f| and |T|, no
+ *       pixel aliases and every fine step's pixel is the reference's;
+ * Prints "pixel_fixed <case> checked N fine F bad B" per case (expected B = 0); the last case is
+ * named "hostile".
  * Build: gcc -O2 -ffp-contract=off -I union-thesis-slam_amd/csrc tools/check_pixel_fixed.c -lm. */
 #include <float.h>
 #include <stdint.h>
@@ -79,6 +86,56 @@ static int setup(Axis* a, int axis, int W, int H, double fx, double fy, double c
     a->E = 8.0 * 0x1p-53 * b[axis];
     a->span = (double)(W > H ? W : H) + fmax(fabs(cx), fabs(cy));
     return 1;
+}
+
+/* (hostile): one frame.  expect_off: 1 the fast path must be off, 0 either; dead: frame_is_dead's answer. */
+static void hostile(const double* T, double fx, double fy, double cx, double cy, int expect_off, int dead, long* n,
+                    long* fine, long* bad) {
+    const int W = 80, H = 60;
+    const double wmax[3] = {2.25, 1.75, 2.25};
+    const double rcp_max = exp2(-24.4);
+    const long bad0 = *bad;
+    ++*n;
+    if (frame_is_dead(T, fx, fy, cx, cy) != dead) ++*bad;
+    const PixelFixed p = pixel_fixed(T, fx, fy, cx, cy, W, H, wmax);
+    if (p.zmin_hi != INT_MAX && expect_off) ++*bad;
+    if (p.zmin_hi != INT_MAX && (!(p.zmin >= 0.0) || !isfinite(p.zmin))) ++*bad;
+    if (p.zmin_hi == INT_MAX || *bad != bad0) {
+        if (*bad != bad0) fprintf(stderr, "hostile: f %g %g c %g %g T3 %g T11 %g: zmin %g\n", fx, fy, cx, cy, T[3], T[11], p.zmin);
+        return;
+    }
+    long long zb = ((long long)p.zmin_hi + 1) << 32;
+    double zmin_q;
+    memcpy(&zmin_q, &zb, sizeof zmin_q);
+    if (!(zmin_q > p.zmin)) ++*bad;
+    for (int axis = 0; axis < 2; ++axis) {
+        const double* t = T + 4 * axis;
+        Axis a;
+        a.p = p;
+        a.c = axis ? cy : cx;
+        a.C = axis ? p.Cy : p.Cx;
+        a.f = axis ? fy : fx;
+        a.side = axis ? H : W;
+        a.m = axis ? p.my : p.mx;
+        /* the numerator's bound, from |f| and |T| (not through fold_rows) */
+        a.bound = fabs(a.f) * (fabs(t[0]) * wmax[0] + fabs(t[1]) * wmax[1] + fabs(t[2]) * wmax[2] + fabs(t[3]));
+        a.E = 8.0 * 0x1p-53 * a.bound;
+        a.span = (double)(W > H ? W : H) + fmax(fabs(cx), fabs(cy));
+        for (int j = 0; j < 4000; ++j, ++*n) {
+            const double z = zmin_q * (1.0 + (j & 3 ? 0.0 : 0.5 * urand()));
+            const double xf = (j & 1 ? 1.0 : -1.0) * a.bound * (j & 2 ? 1.0 : 1.0 - 0.01 * urand());
+            if (!(fabs(xf / z * (1.0 + rcp_max)) + fabs(a.c) + 1.0 < 65536.0 - a.side)) ++*bad;
+            *fine += step(&a, xf, z, j & 4 ? rcp_max : -rcp_max, bad);
+        }
+        const double zhi = fmax(64.0, 1e6 * zmin_q), lz = log(zhi / zmin_q);
+        for (int j = 0; j < 20000; ++j, ++*n) {
+            const double z = zmin_q * exp(lz * urand());
+            double xf = (j & 1) ? ((3.0 * urand() - 1.0) * a.side - a.c) * z : a.bound * srand1();
+            if (fabs(xf) > a.bound) xf = a.bound * srand1();
+            *fine += step(&a, xf, z, rcp_max * srand1(), bad);
+        }
+    }
+    if (*bad != bad0) fprintf(stderr, "hostile: f %g %g c %g %g T3 %g T11 %g: zmin %g, %ld bad\n", fx, fy, cx, cy, T[3], T[11], p.zmin, *bad - bad0);
 }
 
 int main(void) {
@@ -188,5 +245,64 @@ int main(void) {
         }
     }
     printf("pixel_fixed e checked %ld bad %ld\n", n_e, bad_e);
-    return (bad_a | bad_b | bad_c | bad_d | bad_e) != 0;
+    long bad_f = 0, n_f = 0, fine_f = 0;
+    {
+        /* the good rows of tests/hostile_pose.py, frame 0 (a 6 degree turn about y, 2 degrees about x) */
+        const double G[12] = {0.9945218953682733, 0.0, -0.10452846326765347, -0.045,
+                              0.0036479567, 0.9993908270190958, 0.0347081937, -0.02,
+                              0.1044647897, -0.03489949670250097, 0.9939160672, 0.6};
+        const double fx = 60.0, fy = 62.0, cx = 39.5, cy = 29.5;
+        const double nf[3] = {NAN, INFINITY, -INFINITY};
+        hostile(G, fx, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        if (pixel_fixed(G, fx, fy, cx, cy, 80, 60, (const double[3]){2.25, 1.75, 2.25}).zmin_hi == INT_MAX) ++bad_f; /* the control */
+        double T[12];
+        for (int k = 0; k < 3; ++k) { /* NaN / +-inf: everywhere, then in each translation entry alone */
+            for (int r = 0; r < 12; ++r) T[r] = nf[k];
+            hostile(T, fx, fy, cx, cy, 1, 1, &n_f, &fine_f, &bad_f);
+            for (int r = 3; r < 12; r += 4) {
+                memcpy(T, G, sizeof T);
+                T[r] = nf[k];
+                hostile(T, fx, fy, cx, cy, 1, 1, &n_f, &fine_f, &bad_f);
+            }
+            hostile(G, nf[k], fy, cx, cy, 1, 1, &n_f, &fine_f, &bad_f);
+            hostile(G, fx, nf[k], cx, cy, 1, 1, &n_f, &fine_f, &bad_f);
+            hostile(G, fx, fy, nf[k], cy, 1, 1, &n_f, &fine_f, &bad_f);
+            hostile(G, fx, fy, cx, nf[k], 1, 1, &n_f, &fine_f, &bad_f);
+        }
+        const double huge[4] = {1e30, 1e39, 1e300, 1e307};
+        for (int k = 0; k < 4; ++k) { /* finite rows; at 1e307 T * f overflows: no fast path */
+            memcpy(T, G, sizeof T);
+            T[3] = huge[k]; T[7] = -huge[k]; T[11] = huge[k];
+            hostile(T, fx, fy, cx, cy, k == 3, 0, &n_f, &fine_f, &bad_f);
+        }
+        memcpy(T, G, sizeof T);
+        T[8] = T[9] = T[10] = T[11] = 0.0; /* z == 0 everywhere */
+        hostile(T, fx, fy, cx, cy, 0, 1, &n_f, &fine_f, &bad_f);
+        memset(T, 0, sizeof T);
+        hostile(T, fx, fy, cx, cy, 0, 1, &n_f, &fine_f, &bad_f);
+        T[11] = 1.0; /* (a zero rotation in front of the camera is a frame like any other) */
+        hostile(T, fx, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        /* non-rigid rows A * G about (0, 0, 1): scales, a shear, a mirror */
+        const double A[5][9] = {{2, 0, 0, 0, 2, 0, 0, 0, 2}, {0.5, 0, 0, 0, 0.5, 0, 0, 0, 0.5}, {1, 0, 0, 0, 2, 0, 0, 0, 0.5},
+                                {1, 0.35, 0, 0, 1, 0.25, 0.2, 0, 1}, {-1, 0, 0, 0, 1, 0, 0, 0, 1}};
+        for (int k = 0; k < 5; ++k) {
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 4; ++c)
+                    T[4 * r + c] = A[k][3 * r] * G[c] + A[k][3 * r + 1] * G[4 + c] + A[k][3 * r + 2] * G[8 + c] +
+                                   (c == 3 ? (r == 2 ? 1.0 : 0.0) - A[k][3 * r + 2] : 0.0);
+            hostile(T, fx, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        }
+        /* intrinsics */
+        hostile(G, -fx, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, fx, -fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, -fx, -fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, -6000.0, -6200.0, cx, cy, 0, 0, &n_f, &fine_f, &bad_f); /* (negative and large: the bound matters) */
+        hostile(G, 0.0, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, (double)1e-30f, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, (double)1e30f, fy, cx, cy, 0, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, fx, fy, 70000.0, cy, 1, 0, &n_f, &fine_f, &bad_f);
+        hostile(G, fx, fy, (double)1e30f, cy, 1, 0, &n_f, &fine_f, &bad_f);
+    }
+    printf("pixel_fixed hostile checked %ld fine %ld bad %ld\n", n_f, fine_f, bad_f);
+    return (bad_a | bad_b | bad_c | bad_d | bad_e | bad_f) != 0;
 }

@@ -22,6 +22,10 @@ Fixtures written (data only -- inputs and expected outputs, no reference source)
   golden/hostile_depth.npz     tests/hostile_depth.py's NaN / infinite / negative / tiny / far / huge f64
                                depth frames -> 48x40x24 @ 2 cm, grid CPU path and HashTable.integrate,
                                at 128x96 and 126x95 (G2x)
+  golden/hostile_pose.npz      tests/hostile_pose.py's NaN / infinite / huge / singular / non-rigid poses and
+                               negative / zero / non-finite intrinsics -> 40x24x20 @ 4 cm and 0.0625 m, grid CPU
+                               path on a preloaded volume and HashTable.integrate on a fresh table; their
+                               view frusta and the demo's running bounds (G2p)
   golden/lounge2cm_kat.json    lounge 2 cm, frames 0-9: per-frame counts + final-state digest (G3)
   golden/lounge512_kat.json    lounge f0 -> 512^3 @ 2 cm: count + digest (G5)
   golden/frustum_bounds.npz    lounge frames 0-999: per-frame max depth (mm, after the demo's
@@ -274,6 +278,10 @@ def inner():
     if want("hostile"):
         gen_hostile(grid_fusion, hash_fusion)
 
+    # ---- G2p hostile poses and intrinsics (tests/hostile_pose.py) -----------------------------
+    if want("hostile_pose"):
+        gen_hostile_pose(grid_fusion, hash_fusion)
+
     # ---- G3 lounge 2 cm, 10 frames -----------------------------------------------------
     if want("lounge2cm"):
         vol = grid_fusion.TSDFVolume(np.array(LOUNGE_BNDS), 0.02, use_gpu=False)
@@ -383,6 +391,109 @@ def gen_hostile(grid_fusion, hash_fusion):
               "hash path %.1f s" % t_hash)
     np.savez_compressed(os.path.join(GOLD, "hostile_depth.npz"), **res)
     print("hostile_depth.npz", os.path.getsize(os.path.join(GOLD, "hostile_depth.npz")), "bytes")
+
+
+def gen_hostile_pose(grid_fusion, hash_fusion):
+    """G2p: every case of tests/hostile_pose.py through the reference's CPU TSDFVolume.integrate, on a
+    volume preloaded with the good frames, and through HashTable.integrate on a fresh table; in the
+    "pose" form as the reference takes it, in the "rows" form with np.linalg.inv answering the case's
+    rows for the duration of the call (inv(cam_pose) is the only use integrate makes of the pose).
+    Stored per case and form p = "<name>/<form>/": p + "raised" (the exception's type name, "" if none),
+    p + "nupd", p + "mask" (packed, C order: voxels whose weight the frame changed), p + "sha" (sha256 of
+    the whole tsdf, weight and colour volumes after the frame), p + "hash_mask" (the table's keys) and
+    p + "hash_sha" (sdf, weight, colour of the entries in C order, f64).  Per "pose" form also
+    p + "frustum" (get_view_frustum for a frame whose max depth is the good frame's; NaN where it
+    gives NaN) and p + "frustum_bounds" (the demo's np.minimum / np.amin bounds of that frame alone,
+    from zeros); "frustum_running": the same bounds folded over the cases in "frustum_order" (those
+    whose own bounds hold no NaN first).  The inputs are stored beside them."""
+    import warnings
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import hostile_pose as P
+    real_inv = np.linalg.inv
+    cases = P.frame_cases()
+    res = {"names": np.array(list(cases)), "K_good": P.K, "hw": np.array(P.HW)}
+    pre = {}
+    for vol, (b, vs) in P.VOLUMES.items():
+        v = grid_fusion.TSDFVolume(np.array(b), vs, use_gpu=False)
+        assert tuple(int(d) for d in v._vol_dim) == P.DIMS
+        for f in range(P.PRELOAD):
+            v.integrate(P.rgb(f), P.depth_m(vol, f), P.K, P.good_pose(vol, f))
+        pre[vol] = v
+        res["preload_sha_" + vol] = np.array(digest(v._tsdf_vol_cpu, v._weight_vol_cpu, v._color_vol_cpu))
+        res["preload_n_" + vol] = np.int64((v._weight_vol_cpu > 0).sum())
+    run_b = np.zeros((3, 2))
+    running, frusta = [], {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for name, c in cases.items():
+            vol = c["vol"]
+            b, vs = P.VOLUMES[vol]
+            res[name + "/rows"], res[name + "/K"] = c["rows"], c["K"]
+            if c["pose"] is not None:
+                res[name + "/pose"] = c["pose"]
+            for form in P.forms(c):
+                p = "%s/%s/" % (name, form)
+                v = grid_fusion.TSDFVolume(np.array(b), vs, use_gpu=False)
+                for a in ("_tsdf_vol_cpu", "_weight_vol_cpu", "_color_vol_cpu"):
+                    setattr(v, a, getattr(pre[vol], a).copy())
+                ht = hash_fusion.HashTable(np.array(b), vs, 100000, 0.75, False)
+                pose = c["pose"] if form == "pose" else np.eye(4)
+                if form == "rows":
+                    np.linalg.inv = lambda m, rows=c["rows"]: rows.copy()
+                raised = ""
+                try:
+                    v.integrate(P.rgb(P.PRELOAD), P.depth_m(vol, P.PRELOAD), c["K"], pose)
+                    ht.integrate(P.rgb(P.PRELOAD), P.depth_m(vol, P.PRELOAD), c["K"], pose)
+                except Exception as e:  # (recorded: the drop-in class must raise the same type)
+                    raised = type(e).__name__
+                finally:
+                    np.linalg.inv = real_inv
+                changed = v._weight_vol_cpu.reshape(-1) != pre[vol]._weight_vol_cpu.reshape(-1)
+                res[p + "raised"] = np.array(raised)
+                res[p + "nupd"] = np.int64(changed.sum())
+                res[p + "mask"] = np.packbits(changed)
+                res[p + "sha"] = np.array(digest(v._tsdf_vol_cpu, v._weight_vol_cpu, v._color_vol_cpu))
+                has = np.zeros(P.DIMS, bool)
+                sdf, w, col = np.ones(P.DIMS), np.zeros(P.DIMS), np.zeros(P.DIMS)
+                for bk in ht._hash_table:
+                    if bk is None:
+                        continue
+                    for j in range(5):
+                        e = bk.get_ith_entry(j)
+                        if e is not None and e.get_voxel() is not None:
+                            q = tuple(int(x) for x in e.get_position())
+                            has[q] = True
+                            sdf[q], w[q], col[q] = float(e.get_voxel().get_sdf()), float(e.get_voxel()._weight), float(e.get_voxel().get_color())
+                assert int(has.sum()) == ht.count_num_hash_entries()
+                res[p + "hash_mask"] = np.packbits(has.reshape(-1))
+                res[p + "hash_sha"] = np.array(digest(sdf[has], w[has], col[has]))
+                if form == "pose":
+                    proxy = np.zeros(P.HW)
+                    proxy[0, 0] = float(P.depth_m(vol, P.PRELOAD).max())
+                    vfp = grid_fusion.get_view_frustum(proxy, c["K"], c["pose"])
+                    res[p + "frustum"] = vfp
+                    frusta[name] = vfp
+                print("hostile_pose", p, raised or int(res[p + "nupd"]), "entries", int(has.sum()))
+    # the demo's loop (grid_demo1.py:50-64) from zeros: over each case alone, and over all of them with
+    # the cases whose own bounds hold no NaN first (np.minimum keeps a NaN for good)
+    def fold(b, vfp):
+        b = b.copy()
+        b[:, 0] = np.minimum(b[:, 0], np.amin(vfp, axis=1))
+        b[:, 1] = np.maximum(b[:, 1], np.amax(vfp, axis=1))
+        return b
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for name, vfp in frusta.items():
+            res[name + "/pose/frustum_bounds"] = fold(np.zeros((3, 2)), vfp)
+        order = sorted(frusta, key=lambda n: bool(np.isnan(res[n + "/pose/frustum_bounds"]).any()))
+        for name in order:
+            run_b = fold(run_b, frusta[name])
+            running.append(run_b)
+    res["frustum_order"] = np.array(order)
+    res["frustum_running"] = np.stack(running)
+    np.savez_compressed(os.path.join(GOLD, "hostile_pose.npz"), **res)
+    print("hostile_pose.npz", os.path.getsize(os.path.join(GOLD, "hostile_pose.npz")), "bytes")
 
 
 def gen_frustum(grid_fusion, cam_intr):

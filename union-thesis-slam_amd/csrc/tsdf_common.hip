@@ -513,11 +513,23 @@ int Base::prepare_batch(Batch* bt, const void* depth, int dk, const void* color,
     for (int i = 0; i < n; ++i) {
         Frame* fr = &bt->f[i];
         const double* T = Tinv + 16 * (size_t)(first + i);
-        for (int r = 0; r < 12; ++r) fr->T[r] = T[r];
         fr->fx = (double)(float)K[0];
         fr->fy = (double)(float)K[4];
         fr->cx = (double)(float)K[2];
         fr->cy = (double)(float)K[5];
+        // A frame the reference cannot update a voxel from (frame_is_dead, tsdf_pixel.h: a non-finite
+        // row or intrinsic, or a z that is the same non-positive number everywhere) is integrated as
+        // the zero matrix -- z == 0 for every voxel -- and culled outright below, so that no kernel
+        // meets a NaN pixel (v_cvt_i32_f64 turns NaN into 0, a valid column, where the reference's
+        // astype(int) gives the most negative integer) and the hash inserts no block for it.
+        static const double kDeadT[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        const bool dead = frame_is_dead(T, fr->fx, fr->fy, fr->cx, fr->cy) != 0;
+        if (dead) {
+            T = kDeadT;
+            fr->fx = fr->fy = 1.0;
+            fr->cx = fr->cy = 0.0;
+        }
+        for (int r = 0; r < 12; ++r) fr->T[r] = T[r];
         for (int j = 0; j < 4; ++j) {
             fr->Tf[j] = T[j] * fr->fx;
             fr->Tf[4 + j] = T[4 + j] * fr->fy;
@@ -554,6 +566,7 @@ int Base::prepare_batch(Batch* bt, const void* depth, int dk, const void* color,
         fr->pyr = pyr + (size_t)lay.total * i;
 
         frustum_planes(fr, T, W, H);
+        if (dead) fr->planes[0][3] = -INFINITY;  // cull_brick: 0 * ctr - inf < -rad for every brick
     }
     for (int L = 0; L <= kPyrLevels; ++L) {
         bt->pg.off[L] = lay.off[L];

@@ -696,9 +696,12 @@ __device__ __forceinline__ void project_part(double trunc, const Frame& fr, doub
                 const double y = fr.T[7] + fma(fr.T[6], pz, a1);
                 const int iu = cvt_i32_sat(rint((x * fr.fx) / zc[k] + fr.cx));  // the reference's own operation order
                 const int iv = cvt_i32_sat(rint((y * fr.fy) / zc[k] + fr.cy));
-                // unsigned bounds on the saturated indices (they come from integral, non-NaN
-                // values wherever z > 0: the exact path yields NaN only for a non-finite pose,
-                // whose z -- np.linalg.inv: all NaN -- fails z > 0).  The index itself, not the
+                // unsigned bounds on the saturated indices.  v_cvt_i32_f64 turns NaN into 0, a
+                // valid column, where the reference's astype(int) gives the most negative integer:
+                // prepare_batch keeps NaN out of here by integrating every frame with a non-finite
+                // row or intrinsic as a culled no-op (frame_is_dead, tsdf_pixel.h).  Not covered:
+                // finite rows whose x and z both overflow to infinity for a voxel (inf / inf).
+                // The index itself, not the
                 // packed pair, so that images of any accepted size (sides < 2^24, < 2^28 pixels)
                 // pass here; ~0 marks a pixel outside
                 const bool inb = (unsigned)iu < (unsigned)W && (unsigned)iv < (unsigned)H;

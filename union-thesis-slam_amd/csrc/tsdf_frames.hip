@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kMaxWG) void k_frame_max(const void* depth, long lo
 }
 
 // One thread per frame: grid_fusion.py:371-383 then the demo's min/max (keys[0..2] = min x,y,z;
-// keys[3..5] = max x,y,z).
+// keys[3..5] = max x,y,z; keys[6..8] != 0: the axis holds a NaN coordinate that the pose or K made).
 __global__ void k_frustum(int n, int H, int W, const double* __restrict__ K,
                           const double* __restrict__ poses, const unsigned long long* __restrict__ maxk,
                           double* __restrict__ pts, unsigned long long* bkeys) {
@@ -87,6 +87,7 @@ __global__ void k_frustum(int n, int H, int W, const double* __restrict__ K,
     const double us[5] = {0.0, 0.0, 0.0, (double)W, (double)W};
     const double vs[5] = {0.0, 0.0, (double)H, 0.0, (double)H};
     double lo[3] = {1.0 / 0.0, 1.0 / 0.0, 1.0 / 0.0}, hi[3] = {-1.0 / 0.0, -1.0 / 0.0, -1.0 / 0.0};
+    unsigned nan_axis = 0;
     for (int j = 0; j < 5; ++j) {
         const double z = j == 0 ? 0.0 : dmax;
         const double x = ((us[j] - K[2]) * z) / K[0];
@@ -97,14 +98,24 @@ __global__ void k_frustum(int n, int H, int W, const double* __restrict__ K,
             if (pts) pts[15 * (long long)f + 5 * r + j] = c;
             // an infinite dmax gives infinite coordinates, and NaN ones where it meets a zero
             // (0 * inf, inf - inf): the points report both, the bounds fold the infinities and
-            // pass over the NaNs (fmin / fmax return the other operand; point 0 is always finite)
+            // pass over the NaNs (fmin / fmax return the other operand)
             lo[r] = fmin(lo[r], c);
             hi[r] = fmax(hi[r], c);
+            // a NaN that a depth of 1 m gives as well is the pose's or K's, not the depth's: it
+            // marks the axis, and the bounds come back NaN there as the demo's np.minimum / np.amin
+            // leave them
+            if (c != c) {
+                const double z1 = j == 0 ? 0.0 : 1.0;
+                const double x1 = ((us[j] - K[2]) * z1) / K[0], y1 = ((vs[j] - K[5]) * z1) / K[4];
+                const double c1 = fma(t[3], 1.0, fma(t[2], z1, fma(t[1], y1, t[0] * x1)));
+                if (c1 != c1) nan_axis |= 1u << r;
+            }
         }
     }
     for (int r = 0; r < 3; ++r) {
         atomicMin(bkeys + r, dkey(lo[r]));
         atomicMax(bkeys + 3 + r, dkey(hi[r]));
+        if ((nan_axis >> r) & 1u) atomicMax(bkeys + 6 + r, 1ull);
     }
 }
 
@@ -146,7 +157,7 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     const int chunk = dptr ? n_frames : std::min(n_frames, 64);
     int cu = 256;
     (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev);
-    std::vector<unsigned long long> hk(n_frames), hb(6);  // (read back: declared before the owners)
+    std::vector<unsigned long long> hk(n_frames), hb(9);  // (read back: declared before the owners)
     CallStream cs;
     TSDF_HIP(hipStreamCreateWithFlags(&cs.s, hipStreamNonBlocking));
     hipStream_t s = cs.s;
@@ -155,7 +166,7 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     double *dK = nullptr, *dpose = nullptr, *dpts = nullptr;
     char* stage = nullptr;
     TSDF_TRY(bufs.alloc(&maxk, (size_t)n_frames));
-    TSDF_TRY(bufs.alloc(&bk, 6));
+    TSDF_TRY(bufs.alloc(&bk, 9));
     TSDF_TRY(bufs.alloc(&dK, 9));
     TSDF_TRY(bufs.alloc(&dpose, 16 * (size_t)n_frames));
     if (frustum_pts) TSDF_TRY(bufs.alloc(&dpts, 15 * (size_t)n_frames));
@@ -164,7 +175,7 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     TSDF_HIP(hipMemcpyAsync(dpose, cam_poses, sizeof(double) * 16 * n_frames, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_init_keys, dim3((n_frames + 255) / 256), dim3(256), 0, s, maxk, n_frames, 0ull);
     hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk, 3, ~0ull);
-    hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk + 3, 3, 0ull);
+    hipLaunchKernelGGL(k_init_keys, dim3(1), dim3(64), 0, s, bk + 3, 6, 0ull);
     TSDF_HIP(hipGetLastError());
     // enough workgroups per frame to stream the image at full HBM rate
     const unsigned per_frame = (unsigned)std::max(1ll, std::min<long long>((npx + 4095) / 4096, std::max(1, 4 * cu / std::max(1, chunk))));
@@ -184,16 +195,20 @@ int tsdf_frustum_bounds(const void* depth, int depth_kind, int n_frames, int hei
     hipLaunchKernelGGL(k_frustum, dim3((n_frames + 63) / 64), dim3(64), 0, s, n_frames, height, width, (const double*)dK,
                        (const double*)dpose, (const unsigned long long*)maxk, dpts, bk);
     TSDF_HIP(hipGetLastError());
-    TSDF_HIP(hipMemcpyAsync(hb.data(), bk, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost, s));
+    TSDF_HIP(hipMemcpyAsync(hb.data(), bk, sizeof(unsigned long long) * 9, hipMemcpyDeviceToHost, s));
     if (max_depth) TSDF_HIP(hipMemcpyAsync(hk.data(), maxk, sizeof(unsigned long long) * n_frames, hipMemcpyDeviceToHost, s));
     if (frustum_pts) TSDF_HIP(hipMemcpyAsync(frustum_pts, dpts, sizeof(double) * 15 * n_frames, hipMemcpyDeviceToHost, s));
     TSDF_HIP(hipStreamSynchronize(s));
     if (max_depth)
         for (int f = 0; f < n_frames; ++f) max_depth[f] = frame_max_of(hk[f]);
     // the demo's np.minimum / np.maximum with the incoming bounds (it starts from zeros)
+    // (np.minimum keeps a NaN: incoming NaN bounds stay, and an axis the pose or K made NaN becomes one)
     for (int r = 0; r < 3; ++r) {
-        bounds[2 * r] = std::fmin(bounds[2 * r], dval(hb[r]));
-        bounds[2 * r + 1] = std::fmax(bounds[2 * r + 1], dval(hb[3 + r]));
+        for (int k = 0; k < 2; ++k) {
+            double& b = bounds[2 * r + k];
+            if (hb[6 + r] != 0ull || b != b) b = std::nan("");
+            else b = k == 0 ? std::fmin(b, dval(hb[r])) : std::fmax(b, dval(hb[3 + r]));
+        }
     }
     return TSDF_OK;
 }

@@ -29,11 +29,11 @@ static inline double frame_margin(int W, int H, double cx, double cy) {
 }
 
 /* |X| <= f * (|T0| X + |T1| Y + |T2| Z + |T3|) for world coordinates bounded by (X, Y, Z): the
- * bound of the x (out[0]) and y (out[1]) numerators. */
+ * bound of the x (out[0]) and y (out[1]) numerators (|f|: a negative focal length mirrors the image). */
 static inline void fold_rows(const double* T, double fx, double fy, const double wmax[3], double out[2]) {
     for (int r = 0; r < 2; ++r) {
         const double* t = T + 4 * r;
-        out[r] = (r == 0 ? fx : fy) *
+        out[r] = fabs(r == 0 ? fx : fy) *
                  (fabs(t[0]) * wmax[0] + fabs(t[1]) * wmax[1] + fabs(t[2]) * wmax[2] + fabs(t[3]));
     }
 }
@@ -47,6 +47,20 @@ static inline double fold_bound(const double* T, double fx, double fy, const dou
     double b[2];
     fold_rows(T, fx, fy, wmax, b);
     return 4.0 * (8.0 * 0x1p-53 * fmax(b[0], b[1])) / margin;
+}
+
+/* A frame from which the reference updates no voxel whatever the depth image holds:
+ *  - a non-finite entry in rows 0..2 of inv(cam_pose) or in fx, fy, cx, cy: the entry reaches every
+ *    voxel's x, y or z (0 * inf and inf - inf are NaN), a non-finite x or y gives a non-finite u or v,
+ *    whose np.rint(.).astype(int) is the most negative integer and fails 0 <= u; z = NaN or -inf fails
+ *    z > 0, and z = +inf fails depth - z >= -trunc for every depth (inf - inf is NaN);
+ *  - a zero third row with T[11] <= 0: z is that number for every voxel and fails z > 0.
+ * prepare_batch integrates such a frame as the zero matrix and culls it outright. */
+static inline int frame_is_dead(const double* T, double fx, double fy, double cx, double cy) {
+    int finite = isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy);
+    for (int r = 0; r < 12; ++r) finite = finite && isfinite(T[r]);
+    if (!finite) return 1;
+    return T[8] == 0.0 && T[9] == 0.0 && T[10] == 0.0 && !(T[11] > 0.0);
 }
 
 #define TSDF_PIXEL_BIAS 0x1.8p36 /* 1.5 * 2^36 */
@@ -95,7 +109,9 @@ static inline PixelFixed pixel_fixed(const double* T, double fx, double fy, doub
     fold_rows(T, fx, fy, wmax, b);
     const double denx = 65536.0 - (double)W - fabs(cx) - 2.0, deny = 65536.0 - (double)H - fabs(cy) - 2.0;
     if (!(denx >= 1.0) || !(deny >= 1.0)) return p;
-    const double zmin = fmax(fold_bound(T, fx, fy, wmax, margin), fmax(b[0] / denx, b[1] / deny));
+    /* (at least 2^-1000: rows 0 and 1 may be zero -- fx == 0, the zero matrix -- and the bounds with
+     * them; 1 / z must stay finite, or the numerator's exact 0 times an infinite reciprocal is NaN) */
+    const double zmin = fmax(fmax(fold_bound(T, fx, fy, wmax, margin), fmax(b[0] / denx, b[1] / deny)), 0x1p-1000);
     double Cx, Cy;
     const int mx = pixel_axis(cx, margin, &Cx), my = pixel_axis(cy, margin, &Cy);
     if (mx < 0 || my < 0 || !isfinite(zmin) || !(zmin < 1e300)) return p;

@@ -679,6 +679,24 @@ int check_params(const tsdf_icp_params_t* p) {
     return TSDF_OK;
 }
 
+// The guess of a track is a camera pose: its rotation must be one.  A scaled, sheared, mirrored, zero
+// or NaN rotation block makes systems the solver steps to nowhere from (a guess scaled by (1, 2, 0.5)
+// gave cond(A) = 6e15 and a step of 37 km), so it is refused like the merge's transform.  The tolerance
+// admits poses read from text with about eight digits ((R^T R - I) up to 1.5e-4 in the lounge
+// sequence); the translation is not looked at: a NaN or infinite one finds no inlier and ends lost.
+int check_guess(const double* T) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double d = (T[i] * T[j] + T[4 + i] * T[4 + j]) + T[8 + i] * T[8 + j];
+            if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-3))
+                return set_error(TSDF_E_ARG, "the rotation of pose_guess is not orthonormal ((R^T R)[%d][%d] = %.9g)", i, j, d);
+        }
+    const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) +
+                       T[2] * (T[4] * T[9] - T[5] * T[8]);
+    if (!(std::fabs(det - 1.0) <= 1e-3)) return set_error(TSDF_E_ARG, "the rotation of pose_guess has determinant %.9g, not +1", det);
+    return TSDF_OK;
+}
+
 int check_color_params(const tsdf_icp_color_params_t* q) {
     if (!q) return set_error(TSDF_E_ARG, "null color params pointer");
     if (!(q->color_weight >= 0.0) || !std::isfinite(q->color_weight))
@@ -874,6 +892,7 @@ int track(const RaySource& S, int (*cast)(void*, int, int, const double*, const 
         return set_error(TSDF_E_ARG, "the colour term needs a model map of at least 4x4 (got %dx%d)", H, W);
     TSDF_TRY(check_params(p));
     if (rgbd) TSDF_TRY(check_color_params(q));
+    TSDF_TRY(check_guess(pose_guess));
     IcpCtx& c = handle_ctx(B);
     const size_t px = (size_t)H * W;
     const bool dev = (flags & TSDF_DEVICE_PTRS) != 0;
